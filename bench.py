@@ -15,10 +15,12 @@ batches -- more than 256 MB of text in all, so a step reads its text from HBM, n
 re-fed batch would sit in.  With N > 1 every rank encodes its own shards of the same size (weak scaling) and the step
 includes the all-gather of the ragged token ids over RCCL/xGMI (openvino_tokenizers_amd/distributed.py);
 `value` = units of all ranks / max-over-ranks time.
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries, measured after the timed region: the per-kernel
-one-stream leg behind `roofline`, `stress` (uniform-random text; piece memo off), `end_to_end` (pinned host buffers in
-and out over PCIe) and the CPU baselines (1 core, and all host cores sharing one tokenizer).  The oracle is used only for
-the cpu_baseline legs and a parity spot-check.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line.  With --full the
+line also carries, measured after the timed region: the 200 further steps of `steady`, the per-kernel wall times of
+`kernel_ms` and, at N = 1, the one-stream leg behind `roofline`, `stress` (uniform-random text; piece memo off),
+`end_to_end` (pinned host buffers in and out over PCIe), the CPU baselines (1 core, and all host cores sharing one
+tokenizer) and a parity spot-check against the oracle.  The oracle is used only for those legs.
+--dump-outputs DIR writes the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB).
 """
 from __future__ import annotations
 
@@ -26,9 +28,11 @@ import argparse
 import ctypes as C
 import json
 import os
+import subprocess
 import sys
 import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 # The encode streams, the exchange stream and RCCL's own stream must not share a hardware queue (kernels of streams that
@@ -64,8 +68,10 @@ class TextBatches:
     def __init__(self, model, rows, nbytes, seeds, dev, lower=False):
         self.rows, self.dev, self.host, self.d, self.rs, self.n_chars = rows, dev, [], [], [], []
         rb, re_ = ragged_rows(rows)
-        for seed in seeds:
-            begins, ends, chars = model.batch(rows, nbytes, seed=seed)
+        # the text of every batch depends on its seed alone: generated on host threads (numpy releases the GIL), in seed order
+        with ThreadPoolExecutor(max(1, min(len(seeds), 8))) as pool:
+            texts = list(pool.map(lambda s: model.batch(rows, nbytes, seed=s), seeds))
+        for begins, ends, chars in texts:
             if lower:
                 chars = np.frombuffer(chars.tobytes().lower(), np.uint8).copy()
             d = [torch.as_tensor(x, device=dev) for x in (rb, re_, begins, ends, chars)]
@@ -105,6 +111,7 @@ class EncodeWorkload:
     `run(rs, out, stream)` are the library calls of the concrete op chain."""
     unit = "MB/s"
     dtype = "u8/int32"
+    outputs = ("begins", "ends", "ids")   # the names of what step() / finish() return (--dump-outputs)
 
     def __init__(self, lib, dev, batches):
         self.lib, self.dev, self.batches = lib, dev, batches
@@ -238,6 +245,7 @@ class PipelineEncode(BpeEncode):
     longest row (the PaddingStep's ReduceMax) -- ONE library call per batch (ovtk_encode_dense_enqueue / _finish: the encode's last
     pass writes the dense tensors, no ragged ids tensor), or with --pipeline-calls 2 the encode and ovtk_encode_tail_run."""
     MAX_LENGTH = 1024
+    outputs = ("input_ids", "attention_mask")
 
     def __init__(self, args, lib, dev, rank):
         super().__init__(args, lib, dev, rank, "gpt2", "zipf", args.rows, args.bytes, 1000, model=SpecialTextModel(1234, "zipf"))
@@ -417,6 +425,7 @@ def make_workload(args, lib, dev, rank):
 class Detokenize:
     """Config 5 chunk: VocabDecoder + ByteFallback + FuzeRagged fused, rows x 2048 ids, rotating id batches."""
     unit, dtype, metric, dominant_hint = "Mtok/s", "int32/u8", "token ids/s detokenized (seq 2048)", "detokenize"
+    outputs = ("begins", "ends", "chars")
 
     def __init__(self, args, lib, dev, rank):
         self.lib, self.dev = lib, dev
@@ -508,6 +517,7 @@ class DetokenizeFull:
     which the reference's int32 char offsets cannot hold in one call (src/vocab_decoder.cpp:62-80).  A step = the whole batch
     through FusedDetokenizer.evaluate_chunked: row chunks below 2^31 output bytes each, pipelined over three HIP streams."""
     unit, dtype, metric, dominant_hint = "Mtok/s", "int32/u8", "token ids/s detokenized (seq 2048)", "detokenize"
+    outputs = ("begins", "ends", "chars")   # (of the step's first chunk)
 
     def __init__(self, args, lib, dev, rank):
         from openvino_tokenizers_amd.ops import FusedDetokenizer
@@ -597,6 +607,7 @@ class DetokenizeFull:
 class RaggedToDenseBench:
     """a7 at config-2 size: the ragged ids of a config-2 batch -> input_ids [rows, T] + attention mask, T = longest row."""
     unit, dtype, metric, dominant_hint = "GB/s", "int32/u8", "algorithmic GB/s (RaggedToDense, config-2 ids)", "ragged_to_dense"
+    outputs = ("input_ids", "attention_mask")
 
     def __init__(self, args, lib, dev, rank):
         self.lib, self.dev = lib, dev
@@ -653,6 +664,7 @@ class RaggedToDenseBench:
 class VocabEncoderBench:
     """a6: VocabEncoder on the words of config-3 text (~3 M words per batch), keys = the BERT-shaped vocabulary."""
     unit, dtype, metric, dominant_hint = "Mwords/s", "u8/int32", "words/s looked up (VocabEncoder, BERT-shaped vocabulary)", "vocab_encoder"
+    outputs = ("values",)
 
     def __init__(self, args, lib, dev, rank):
         self.lib, self.dev = lib, dev
@@ -714,6 +726,7 @@ class SmallBatchLatency:
     of the converted GPT-2 tokenizer sees (device-resident buffers)."""
     unit, dtype, metric, dominant_hint = "us/call", "u8/int32", "latency per blocking encode call (32 x 128-byte strings)", "lookup_fused"
     higher_is_better = False
+    outputs = EncodeWorkload.outputs
 
     def __init__(self, args, lib, dev, rank):
         args2 = argparse.Namespace(**vars(args))
@@ -777,6 +790,40 @@ def run_pipelined(wl, steps, stream_ptrs, depth, first=0, complete=lambda f: f()
             complete(inflight.pop(0))
     while inflight:
         complete(inflight.pop(0))
+
+
+DUMP_BUDGET = (64 << 20) - (1 << 16)   # 64 MB for all files, less room for the .npy headers
+
+
+def dump_outputs(out_dir, names, arrays, budget=DUMP_BUDGET, seed=0):
+    """Writes one step's outputs as <out_dir>/<name>.npy: float32 where every value is exact in it (|x| < 2^24), float64
+    otherwise.  Where they would not all fit in `budget` bytes, the larger ones are cut to a seeded sample of their elements
+    (flattened, positions sorted: the same positions for the same sizes from run to run).  Returns what was written."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = []
+    for name, a in zip(names, arrays):
+        x = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        if x.dtype == np.float64:
+            ft = np.float64
+        elif x.dtype == np.float32 or x.size == 0 or (x.dtype.kind in "iub" and int(np.abs(x.astype(np.int64)).max()) < (1 << 24)):
+            ft = np.float32
+        else:
+            ft = np.float64
+        host.append((name, x, ft))
+    written = {}
+    left, n_left = budget, len(host)
+    for name, x, ft in sorted(host, key=lambda h: h[1].size * np.dtype(h[2]).itemsize):
+        cap = left // n_left // np.dtype(ft).itemsize
+        sampled = x.size > cap
+        if sampled:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(seed).choice(x.size, size=cap, replace=False))]
+        y = x.astype(ft)
+        np.save(out_dir / f"{name}.npy", y)
+        left -= y.nbytes
+        n_left -= 1
+        written[name] = {"shape": list(y.shape), "dtype": np.dtype(ft).name, "sampled": bool(sampled)}
+    return written
 
 
 def timed(fn):
@@ -954,7 +1001,6 @@ def end_to_end_in_child(args):
     """The end_to_end leg in a process of its own: every stream a process has ever created keeps its hardware queue, and the
     streams of the legs before this one would share queues with the leg's own (0.78 ms per batch alone, 0.92 ms
     behind a dozen older streams)."""
-    import subprocess
     cmd = [sys.executable, str(Path(__file__).resolve()), "--e2e-child", "--rows", str(args.rows), "--bytes", str(args.bytes), "--tokenizer",
            args.tokenizer, "--text", args.text, "--batches", "4"] + (["--lib", args.lib] if args.lib else [])
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
@@ -965,7 +1011,7 @@ def end_to_end_in_child(args):
 
 
 def relaunch_argv(n_gpus, argv, port=None):
-    """The command `bench.py --gpus N` replaces itself with when nobody launched it as N ranks (WORLD_SIZE unset): one
+    """The command `bench.py --gpus N` runs as a child process when nobody launched it as N ranks (WORLD_SIZE unset): one
     process per GPU under torch.distributed.run, rendezvous on 127.0.0.1 (the container's hostname may not resolve)."""
     port = port or int(os.environ.get("MASTER_PORT", "0")) or (29500 + os.getpid() % 2000)
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n_gpus}", "--master-addr", "127.0.0.1",
@@ -987,8 +1033,8 @@ def main():
                     help="configs 2 / 4: run the tokenizer's tables behind this model's split pattern instead of its own")
     ap.add_argument("--no-memo", action="store_true", help="config 2: BPETokenizer with cache_capacity=0 (no piece memo)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the all-gather (rank-local consumer)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stress / end_to_end / all-cores legs behind the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the parity spot-check")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the stress / end_to_end / all-cores legs behind the timed region")
     ap.add_argument("--hog", type=int, default=0, help="debug: occupy CU slots with N idle 512-thread blocks on a side stream during "
                                                         "every step (stands in for RCCL's all-gather kernel; tools/cu_hog.hip)")
     ap.add_argument("--row-tickets", type=int, default=-1, help="ovtk_set_row_tickets(n); default 0 (static row assignment)")
@@ -1015,14 +1061,21 @@ def main():
     ap.add_argument("--memo-store", type=int, default=-1, help="ovtk_set_memo_store(n) before the tokenizer is built (debug; default: the library's)")
     ap.add_argument("--e2e-child", action="store_true", help="internal: run only the end_to_end leg and print its JSON object")
     ap.add_argument("--spawn", action="store_true", help="take the `--gpus N` relaunch under torch.distributed.run even for N = 1 (test)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other leg: the 200 steady steps, the per-kernel "
+                    "wall times and the one-stream leg behind `roofline`, the CPU baselines and the parity spot-check, the stress and "
+                    "end_to_end legs (each as --no-cpu-baseline / --no-extras / --no-alone-leg leave it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, 64 MB at most: larger outputs as a "
+                         "fixed seeded sample), rank 0")
     args = ap.parse_args()
     os.environ["OVTK_BENCH_DEPTH"] = str(args.depth)   # the output rings are sized for the batches in flight
 
-    if (args.gpus > 1 or args.spawn) and "WORLD_SIZE" not in os.environ:   # `python bench.py --gpus N`: become N ranks
+    if (args.gpus > 1 or args.spawn) and "WORLD_SIZE" not in os.environ:   # `python bench.py --gpus N`: run as N ranks
         have = torch.cuda.device_count()
         if have < args.gpus:
             sys.exit(f"bench.py --gpus {args.gpus}: this node shows {have} GPU(s)")
-        os.execv(sys.executable, relaunch_argv(args.gpus, sys.argv[1:]))
+        rc = subprocess.run(relaunch_argv(args.gpus, sys.argv[1:])).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
@@ -1095,8 +1148,13 @@ def main():
         return exchange.submit_wire(*res) if to_wire else exchange.submit(*res)
 
     def run_steps(first, n, stamps=None):
+        """-> what the last of the n steps returned (its outputs: the global ones where N > 1 exchanges them)."""
+        last = [None]
+
         def done(f):
-            complete(f)
+            res = complete(f)
+            if res is not None:
+                last[0] = res
             if stamps is not None:
                 stamps.append(time.perf_counter())
         if two_half:
@@ -1114,7 +1172,10 @@ def main():
             for i in range(first, first + n):
                 done(lambda i=i: wl.step(i))
         if exchange is not None:
-            exchange.flush()
+            out = exchange.flush()
+            if out:
+                last[0] = out[-1]
+        return last[0]
 
     def barrier():
         torch.cuda.synchronize()
@@ -1133,16 +1194,22 @@ def main():
     barrier()
     timed_stamps = [] if os.environ.get("OVTK_BENCH_STAMPS") else None   # (a diagnostic: when each of the K batches completed, to stderr)
     t0 = time.perf_counter()
-    run_steps(args.warmup, args.steps, timed_stamps)   # every one of the K batches is complete (and, N > 1, gathered on every rank) when it returns
+    last = run_steps(args.warmup, args.steps, timed_stamps)   # every one of the K batches is complete (and, N > 1, gathered on every rank) when it returns
     barrier()
     dt = time.perf_counter() - t0
     if timed_stamps:
         print("timed region: completions at (us)", [round((x - t0) * 1e6) for x in timed_stamps], "end", round(dt * 1e6), file=sys.stderr)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before any other leg reuses the output buffers
+        if not isinstance(last, (tuple, list)):
+            sys.exit("--dump-outputs: the timed steps handed back no arrays")
+        names = wl.outputs if exchange is None else EncodeWorkload.outputs
+        dumped = dump_outputs(args.dump_outputs, names, last)
     # The same loop for 200 further steps: the K steps above are the reported region -- 1.3 ms of wall time at K = 20,
     # of which one fill of the three-stream pipeline is a visible part --, this leg says what the loop settles at, and how evenly the
     # batches complete (the host-side interval between two completions: its median, and the 90th percentile).
     steady = None
-    if not latency_cfg and world == 1:
+    if args.full and not latency_cfg and world == 1:
         n_steady = 200
         stamps = []
         barrier()
@@ -1158,11 +1225,12 @@ def main():
                   "note": "the same host loop for 200 further steps behind the reported region; not `value`"}
     # per-kernel wall times of the same loop (overlapped launches), collected in a leg of its own behind the timed region
     n_prof = min(args.steps, 48)
-    lib.ovtk_profile_reset()
-    lib.ovtk_profile_enable(1)
-    run_steps(args.warmup + args.steps, n_prof)
-    barrier()
-    lib.ovtk_profile_enable(0)
+    if args.full:
+        lib.ovtk_profile_reset()
+        lib.ovtk_profile_enable(1)
+        run_steps(args.warmup + args.steps, n_prof)
+        barrier()
+        lib.ovtk_profile_enable(0)
     my_units = sum(wl.units(i) for i in range(args.warmup, args.warmup + args.steps))
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -1183,8 +1251,8 @@ def main():
     # rocprofv3 --kernel-trace --stats reproduces for `bench.py --streams 1`, profiles/); the timed loop's own events are of
     # launches that share the CUs with the neighbouring batches' kernels (the point of the streams) and are reported as
     # `overlapped` for information only.
-    prof = profile_table(lib)
-    kernels = {k: round(v[0] / max(v[1], 1), 4) for k, v in prof.items()}
+    prof = profile_table(lib) if args.full else {}
+    kernels = {k: round(v[0] / max(v[1], 1), 4) for k, v in prof.items()} if args.full else None
     per_step = {k: v[0] / n_prof for k, v in prof.items()}
     roofline = None
     if per_step:
@@ -1257,7 +1325,7 @@ def main():
     # ---- parity spot-check + CPU baselines (oracle = "port" of the reference's algorithm) + extra legs, rank 0, N = 1
     cpu_baseline, cpu_all, parity, stress, e2e = None, None, None, None, None
     cpu_all_private, cpu_curve = None, None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         n_s = wl.sample_rows
         ref, cdt, sample_units, what, passes = cpu_one_core(wl, n_s)
         res = wl.step(0)
@@ -1283,7 +1351,7 @@ def main():
             cpu_all = cpu_all_cores(wl)
             cpu_all_private = cpu_all_cores(wl, seconds=6.0, private=True)
             cpu_curve = cpu_thread_curve(wl)
-    if world == 1 and not args.no_extras and args.config == "2" and args.text == "zipf" and not args.no_memo:
+    if args.full and world == 1 and not args.no_extras and args.config == "2" and args.text == "zipf" and not args.no_memo:
         stress = {}
         from tools.workloads import MODEL_PATTERNS
         legs = [("uniform_text", dict(kind="uniform")), ("no_memo", dict(kind="zipf", no_memo=True)),
@@ -1355,9 +1423,12 @@ def main():
         "roofline": roofline, "cpu_baseline": cpu_baseline, "cpu_baseline_all_cores": cpu_all, "cpu_baseline_all_cores_private": cpu_all_private,
         "cpu_baseline_thread_curve": cpu_curve, "stress": stress, "end_to_end": e2e,
         "parity_prefix_bit_exact": parity,
-        "parity_per_chunk": (wl.parity_per_chunk() if hasattr(wl, "parity_per_chunk") and world == 1 and not args.no_cpu_baseline else None),
+        "parity_per_chunk": (wl.parity_per_chunk() if args.full and hasattr(wl, "parity_per_chunk") and world == 1 and not args.no_cpu_baseline else None),
         "kernel_ms": kernels,
+        "full": args.full,
     }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": str(args.dump_outputs), "step": args.warmup + args.steps - 1, "files": dumped}
     op_t, op_x = C.c_int64(), C.c_int64()
     L.check(lib, lib.ovtk_short_path_stats(C.byref(op_t), C.byref(op_x)))
     line["config"]["short_path"] = {"mode": args.short_path, "calls_tried": int(op_t.value), "calls_that_needed_no_other_kernel": int(op_x.value),

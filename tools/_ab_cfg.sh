@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for cfg in ${CFGS:-2 3 4 pipeline}; do
   for m in ${MODES:-0 1}; do
-    python bench.py --config $cfg --steps 50 --warmup 10 --no-extras --no-cpu-baseline --short-path $m > $OUT/bench_c${cfg}_sp$m.json 2> $OUT/bench_c${cfg}_sp$m.err
+    python bench.py --config $cfg --steps 50 --warmup 10 --no-extras --no-cpu-baseline --full --short-path $m > $OUT/bench_c${cfg}_sp$m.json 2> $OUT/bench_c${cfg}_sp$m.err
     python - <<PY
 import json
 try:

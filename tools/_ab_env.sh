@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for v in $VALS; do
   for st in ${STREAMS:-3 1}; do
-    env $VAR=$v python bench.py --steps ${STEPS:-50} --warmup 10 --no-extras --no-cpu-baseline --streams $st $ARGS > $OUT/bench_${VAR}_${v}_s$st.json 2> $OUT/bench_${VAR}_${v}_s$st.err
+    env $VAR=$v python bench.py --steps ${STEPS:-50} --warmup 10 --no-extras --no-cpu-baseline --full --streams $st $ARGS > $OUT/bench_${VAR}_${v}_s$st.json 2> $OUT/bench_${VAR}_${v}_s$st.err
     python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ mkdir -p $OUT
 python -m pytest tests/test_short_path.py -m gpu -x -q > $OUT/t_short_path.log 2>&1; tail -3 $OUT/t_short_path.log
 for m in 0 1 0 1; do
   for st in 3 1; do
-    python bench.py --steps 50 --warmup 10 --no-extras --no-cpu-baseline --short-path $m --streams $st > $OUT/bench_c2_op${m}_s$st.json 2> $OUT/bench_c2_op${m}_s$st.err
+    python bench.py --steps 50 --warmup 10 --no-extras --no-cpu-baseline --full --short-path $m --streams $st > $OUT/bench_c2_op${m}_s$st.json 2> $OUT/bench_c2_op${m}_s$st.err
     python - <<PY
 import json
 d=json.loads(open("$OUT/bench_c2_op${m}_s$st.json").read().strip().splitlines()[-1])

@@ -16,16 +16,16 @@ if [ "${1:-run}" = build ]; then
   done
   exit 0
 fi
-mkdir -p gpurun_out/r03/lds
+OUT=$(mktemp -d)
 for rep in 1 2; do
-  python bench.py --steps 60 --warmup 16 --no-cpu-baseline --no-extras > gpurun_out/r03/lds/base_$rep.json 2>/dev/null
+  python bench.py --steps 60 --warmup 16 --no-cpu-baseline --no-extras --full > "$OUT/base_$rep.json" 2>/dev/null
   for v in $VARIANTS; do
-    python bench.py --steps 60 --warmup 16 --no-cpu-baseline --no-extras --lib tools/build/libovtk_${v%%:*}.so > gpurun_out/r03/lds/${v%%:*}_$rep.json 2>/dev/null
+    python bench.py --steps 60 --warmup 16 --no-cpu-baseline --no-extras --full --lib tools/build/libovtk_${v%%:*}.so > "$OUT/${v%%:*}_$rep.json" 2>/dev/null
   done
 done
-python - <<'PY'
-import glob, json
-for f in sorted(glob.glob("gpurun_out/r03/lds/*.json")):
+python - "$OUT" <<'PY'
+import glob, json, sys
+for f in sorted(glob.glob(sys.argv[1] + "/*.json")):
     d = json.load(open(f)); r = d["roofline"]
     print(f.split("/")[-1], "ms_per_step", d["ms_per_step"], "one-stream kernels", r["one_stream_kernel_ms"])
 PY

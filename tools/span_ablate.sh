@@ -5,7 +5,7 @@
 # (A version with shader-clock timers per section was tried first: the compiler moves the ALU work across the clock reads.)
 set -e
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out/r04
+OUT=$(mktemp -d)
 rm -rf openvino_tokenizers_amd/csrc/build/ablsrc
 mkdir -p openvino_tokenizers_amd/csrc/build/ablsrc/openvino_tokenizers_amd/csrc openvino_tokenizers_amd/csrc/build/ablsrc/include
 cp openvino_tokenizers_amd/csrc/*.hpp openvino_tokenizers_amd/csrc/*.cpp openvino_tokenizers_amd/csrc/*.inc openvino_tokenizers_amd/csrc/build/ablsrc/openvino_tokenizers_amd/csrc/
@@ -20,11 +20,11 @@ for v in 1 2 3; do
 done
 for v in 0 1 2 3; do
   if [ $v = 0 ]; then lib=$PWD/openvino_tokenizers_amd/csrc/build/libovtk_amd.so; else lib=$PWD/openvino_tokenizers_amd/csrc/build/abl$v/libovtk_amd.so; fi
-  OVTK_AMD_LIB=$lib timeout 200 python bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-extras > gpurun_out/r04/abl$v.json 2>/dev/null || true
+  OVTK_AMD_LIB=$lib timeout 200 python bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-extras --full > "$OUT/abl$v.json" 2>/dev/null || true
   python - <<PY
 import json
 try:
-    d = json.loads(open('gpurun_out/r04/abl$v.json').read().strip().splitlines()[-1])
+    d = json.loads(open('$OUT/abl$v.json').read().strip().splitlines()[-1])
     print('ablation $v: step', d['ms_per_step'], 'ms; kernels alone', d['roofline'].get('one_stream_kernel_ms'))
 except Exception as e:
     print('ablation $v failed', e)
