@@ -452,6 +452,29 @@ int ovtk_trie_tokenizer_run(ovtk_trie_tokenizer* h, const ovtk_ragged_strings* i
                             void* stream);
 void ovtk_trie_tokenizer_destroy(ovtk_trie_tokenizer* h);
 
+/* ---------------------------------------------------------------- UnigramTokenizer (XLM-RoBERTa, T5, ALBERT ...)
+ * Replaces UnigramTokenizer::evaluate, src/unigram_tokenizer.cpp:17-77, with the algorithm of tokenize_into, :147-224, and the
+ * table of :92-131: per string the best path through the lattice of vocabulary tokens (token id = position in `vocab`), scores
+ * added in float32 and compared strictly (:185: of equal sums the earliest start wins), characters stepped by the lead byte's high
+ * nibble alone (:85-87), an unknown edge of min(scores) - 10 where no token is exactly the character (:157, :197-205), and an id
+ * equal to unk_token_id dropped where it directly follows another one on the way back (:216-219).  Bit-exact, quirks included.
+ * byte_fallback and fuse_unk are stored by the reference and read nowhere in evaluate(); they are accepted and ignored here too.
+ * This library's choices where the reference leaves the answer to its trie builder and an unstable sort (:111-127): a vocabulary
+ * string that occurs more than once answers with its LOWEST id; an empty vocabulary string never matches.  Non-finite scores are
+ * outside the contract.  Limits: fewer than 4 194 303 entries, none longer than 1 023 bytes (OVTK_E_UNSUPPORTED).
+ * `vocab` and `scores` (float32, one per entry) are host memory, consumed at create like the reference's lazy init (:21-36).
+ * out->data capacity: the reference allocates in->strings.n_chars ids (:51); OVTK_E_CAPACITY where it would assert (:69). */
+typedef struct ovtk_unigram ovtk_unigram;
+typedef struct ovtk_unigram_params {
+    int32_t unk_token_id;
+    int byte_fallback;
+    int fuse_unk;
+} ovtk_unigram_params;
+int ovtk_unigram_create(const ovtk_strings* vocab, const float* scores, const ovtk_unigram_params* params, int device,
+                        ovtk_unigram** out);
+int ovtk_unigram_run(ovtk_unigram* h, const ovtk_ragged_strings* in, ovtk_ragged_i32_out* out, int mem, void* stream);
+void ovtk_unigram_destroy(ovtk_unigram* h);
+
 /* ---------------------------------------------------------------- UTF8Validate
  * Replaces UTF8Validate::evaluate, src/utf8_validate.cpp:18-143.  replace_mode 0: drop invalid bytes, 1: U+FFFD.
  * out->begins/ends: [in->n]; out->chars capacity: the reference allocates 3 * in->n_chars (:31-33).  Offsets start

@@ -69,6 +69,10 @@ class VocabDecoderParams(C.Structure):
     _fields_ = [("vocab", Strings), ("skip_tokens", C.c_void_p), ("n_skip_tokens", C.c_int64), ("device", C.c_int)]
 
 
+class UnigramParams(C.Structure):
+    _fields_ = [("unk_token_id", C.c_int32), ("byte_fallback", C.c_int), ("fuse_unk", C.c_int)]
+
+
 class StringsOut(C.Structure):
     _fields_ = [("begins", C.c_void_p), ("ends", C.c_void_p), ("chars", C.c_void_p), ("chars_capacity", C.c_int64),
                 ("n_chars", C.c_int64)]
@@ -106,6 +110,7 @@ EXPORTS = [
     "ovtk_byte_fallback", "ovtk_fuze_ragged", "ovtk_detokenize_run", "ovtk_detokenize_enqueue", "ovtk_detokenize_finish",
     "ovtk_utf8_validate", "ovtk_truncate", "ovtk_combine_segments", "ovtk_encode_tail_run",
     "ovtk_trie_tokenizer_create", "ovtk_trie_tokenizer_run", "ovtk_trie_tokenizer_destroy",
+    "ovtk_unigram_create", "ovtk_unigram_run", "ovtk_unigram_destroy",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",

@@ -725,6 +725,47 @@ class TrieTokenizer(_Op):
         return [ob[:out.n_rows], oe[:out.n_rows], ids[:out.n_data]]
 
 
+class UnigramTokenizer(_Op):
+    """Reference: src/unigram_tokenizer.cpp (evaluate :17-77, tokenize_into :147-224).  Inputs: ragged strings (5), vocab (3),
+    vocab_probs f32 (token id = position in the vocabulary).  Outputs: begins, ends, ids.  Attributes as the reference's
+    (unigram_tokenizer.hpp): byte_fallback and fuse_unk are stored and, as there, change nothing; min_score likewise (the unknown
+    score comes from the minimum of the scores given, :118-122, :157)."""
+
+    def __init__(self, byte_fallback=False, unk_token_id=0, fuse_unk=True, min_score=float("inf"), device=0, lib=None):
+        super().__init__(device, lib)
+        self.byte_fallback, self.unk_token_id, self.fuse_unk, self.min_score = bool(byte_fallback), int(unk_token_id), bool(fuse_unk), float(min_score)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ovtk_unigram_destroy(self._h)
+            self._h = None
+
+    def _ensure(self, inputs):
+        if self._h:
+            return
+        keep = []
+        vocab = _strings_struct(inputs[5], inputs[6], inputs[7], keep)
+        probs = _host(inputs[8], np.float32).reshape(-1)
+        if len(probs) != vocab.n:
+            raise L.OvtkError(L.E_ARG, "Vocab size must be equal to vocab_probs size")
+        p = L.UnigramParams(self.unk_token_id, int(self.byte_fallback), int(self.fuse_unk))
+        self._chk(self._lib.ovtk_unigram_create(C.byref(vocab), probs.ctypes.data_as(C.c_void_p), C.byref(p), self.device, C.byref(self._h)))
+
+    def evaluate(self, inputs):
+        if len(inputs) != 9:
+            raise L.OvtkError(L.E_ARG, f"Incorrect number of inputs passed to UnigramTokenizer: {len(inputs)}")
+        self._ensure(inputs)
+        m = _Mem(inputs[4])
+        rs, (rb, _, _, _, c) = _ragged_in(m, inputs)
+        ob, pob = m.alloc(len(rb), "i32")
+        oe, poe = m.alloc(len(rb), "i32")
+        cap = len(c)   # unigram_tokenizer.cpp:51
+        ids, pids = m.alloc(cap, "i32")
+        out = L.RaggedI32Out(pob, poe, pids, cap, 0, 0)
+        self._chk(self._lib.ovtk_unigram_run(self._h, C.byref(rs), C.byref(out), m.mem, m.stream))
+        return [ob[:out.n_rows], oe[:out.n_rows], ids[:out.n_data]]
+
+
 def _device_alloc(n, kind, device):
     """Device-side output of the staging ops: a torch CUDA tensor, or -- no GPU in the process: the emulator build,
     whose "device" memory is host memory -- a numpy array."""

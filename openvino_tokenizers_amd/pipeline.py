@@ -104,6 +104,28 @@ class WordPieceTokenizationStep(Step):
         return "ids", self.op.evaluate(list(vals[:5]) + self.consts)
 
 
+class UnigramModelStep(Step):
+    """src/unigram_tokenizer.cpp:17-77 (tokenizer_pipeline.py:826-883).  vocab: the token strings (bytes or str, id = position);
+    vocab_logprobs: one float32 score each.  The reference op has no skips input: a state that carries skips is refused."""
+
+    def __init__(self, vocab, vocab_logprobs, byte_fallback=False, unk_token_id=0, fuse_unk=True, lib=None):
+        words = [w if isinstance(w, bytes) else w.encode() for w in vocab]
+        ends = np.cumsum([len(w) for w in words], dtype=np.int64).astype(np.int32)
+        begins = np.concatenate([[0], ends[:-1]]).astype(np.int32) if len(words) else np.zeros(0, np.int32)
+        probs = np.asarray(vocab_logprobs, np.float32).reshape(-1)
+        if len(probs) != len(words):
+            raise ValueError("UnigramModelStep: vocab and vocab_logprobs differ in length")
+        self.consts = [begins, ends, np.frombuffer(b"".join(words), np.uint8), probs]
+        self.op = K.UnigramTokenizer(byte_fallback=byte_fallback, unk_token_id=unk_token_id, fuse_unk=fuse_unk, lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "strings"
+        if len(vals) > 5 and vals[5] is not None:
+            raise ValueError("UnigramModelStep: the state carries skips (a SpecialTokensSplit in front), and UnigramTokenizer has no skips "
+                             "input: skipped strings would be tokenized like any other")
+        return "ids", self.op.evaluate(list(vals[:5]) + self.consts)
+
+
 class TruncationStep(Step):
     """src/truncate.cpp:37-150, one input."""
 

@@ -3,7 +3,7 @@ on a config-2-shaped batch (65 536 rows x ~512 bytes of zipf text, a GPT-2 speci
 batch for the ops behind the tokenizer), inputs and outputs in HBM:
 
     UTF8Validate (both modes), SpecialTokensSplit (the op: count pass, scan, write pass), RegexSplit (the op), StringTensorPack /
-    StringTensorUnpack, TrieTokenizer, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
+    StringTensorUnpack, TrieTokenizer, UnigramTokenizer, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
     (ovtk_encode_tail_run: Truncate -> CombineSegments -> RaggedToDense x 2 in one call).
 
 Per op one JSON line: wall time per call (Python + the library's host side + the kernels; the call returns when its results are
@@ -138,6 +138,43 @@ def main():
                    lambda out: same(ref_tr[:2], [to_np(out[0])[:k], to_np(out[1])[:k]]) and same([ref_tr[2]], [to_np(out[2])], upto=len(ref_tr[2])),
                    f"V = {len(tok.vocab)} (the GPT-2-shaped vocabulary's strings), a lane per 64-byte segment + a lane per row that stitches them")
     del tr_out
+    # ---- UnigramTokenizer (src/unigram_tokenizer.cpp:17-77): the same batch split on whitespace, a vocabulary from the batch's own lexicon
+    # (all single bytes + its words and their prefixes, scores multiples of 1/64); the check is tests/unigram_ref.py on the first rows
+    from collections import Counter
+    from openvino_tokenizers_amd.ops import UnigramTokenizer
+    from tests.unigram_ref import UnigramRef
+    words = Counter(bytes(c).split())
+    uni_vocab = [bytes([x]) for x in range(256)]
+    known = set(uni_vocab)
+    for wd in words:
+        for ln in range(2, min(len(wd), 64) + 1):
+            if wd[:ln] not in known:
+                known.add(wd[:ln])
+                uni_vocab.append(wd[:ln])
+    uni_scores = (-np.random.default_rng(7).integers(0, 2048, len(uni_vocab)) / 64).astype(np.float32)
+    steps = 0   # edges followed + probes that found none, over every character start of the batch's words
+    for wd, times in words.items():
+        here = 0
+        for p0 in range(len(wd)):
+            if p0 and (wd[p0] & 0xC0) == 0x80:
+                continue
+            ln = 0
+            while p0 + ln < len(wd) and wd[p0:p0 + ln + 1] in known:
+                ln += 1
+            here += ln + (1 if p0 + ln < len(wd) else 0)
+        steps += here * times
+    ws_op = RegexSplit("remove", lib=lib)
+    ws_out = ws_op.evaluate(d + [np.frombuffer(rb"\s+", np.uint8)])
+    n_words = len(ws_out[2])
+    uvb, uve, uvc = pack_strings(uni_vocab)
+    uni = UnigramTokenizer(unk_token_id=0, lib=lib)
+    wb, we = to_np(ws_out[2]), to_np(ws_out[3])
+    ref_u = UnigramRef(uni_vocab, uni_scores, 0)(to_np(ws_out[0])[:k], to_np(ws_out[1])[:k], wb, we, c)
+    timed("UnigramTokenizer", lambda: uni.evaluate(list(ws_out[:5]) + [uvb, uve, uvc, uni_scores]), n_c + 8 * n_words + 16 * n + 4 * n_words,
+          lambda out: same(ref_u[:2], [to_np(out[0])[:k], to_np(out[1])[:k]]) and same([ref_u[2]], [to_np(out[2])], upto=len(ref_u[2])),
+          f"V = {len(uni_vocab)} (256 bytes + the batch's {len(words)} words and their prefixes), {n_words} strings, {steps} trie steps: a lane per byte "
+          "walks the trie, a lane per string relaxes and back-tracks")
+    del ws_out
     # ---- the ids of the batch (the fused encode), then the ops behind the tokenizer
     fused = FusedSplitBPE(RegexSplit("isolate", lib=lib), BPETokenizer(**tok.attrs, lib=lib))
     ib, ie, ids = fused.evaluate(d + [pat], tok.consts)
