@@ -114,6 +114,21 @@ inline int stage_input(Workspace& ws, const ovtk_ragged_strings* in, const uint8
     return OVTK_OK;
 }
 
+// regex_split.cpp:129-143 quirk: an all-empty batch leaves RegexSplit with ragged shape {1} = [0],[0] -- the one row the ops behind
+// it then emit.  Writes that row's begin and end (host or device memory); the caller reports one row.
+inline int empty_batch_row(int32_t* begins, int32_t* ends, int mem, hipStream_t s) {
+    const int32_t zero = 0;
+    if (mem == OVTK_MEM_HOST) {
+        begins[0] = 0;
+        ends[0] = 0;
+    } else {
+        OVTK_HIP(hipMemcpyAsync(begins, &zero, 4, hipMemcpyHostToDevice, s));
+        OVTK_HIP(hipMemcpyAsync(ends, &zero, 4, hipMemcpyHostToDevice, s));
+        OVTK_HIP(hipStreamSynchronize(s));
+    }
+    return OVTK_OK;
+}
+
 inline int grid_for_rows(int n_rows) { return std::max(1, (n_rows + kWavesPerBlock - 1) / kWavesPerBlock); }
 
 inline int finish_status(Workspace& ws, hipStream_t s) {
@@ -261,8 +276,8 @@ inline int grid_deferred_hinted(int full_per_shard, int span_sums, int hint) {
 // into staging, per-row counts; the first one must be launched with `grid` blocks, the geometry prep summed over) ->
 // count_scan (final offsets) -> compact.  Workspace overflows reported
 // by the kernels are handled by growing the buffer and running again.
-// self_alloc: the middle's first kernel (lookup_kernel) validates the offsets and takes its staging from bump allocators
-// itself, so no prep launch is needed.
+// A run with a launch plan (EncodePlan, below: the fused encodes): the middle's first kernel (lookup_kernel) validates the offsets and
+// takes its staging from bump allocators itself, so no prep launch is needed.
 //
 // A run is an object so that a call can be split in two (ovtk_encode_enqueue / ovtk_encode_finish): start() stages the
 // inputs and launches one attempt without waiting; finish() waits for that attempt's event (not for whatever the
@@ -279,10 +294,91 @@ inline std::atomic<int>& short_path_mode() {
     return v;
 }
 
-// Calls for which a kernel of the middle is still launched after a call that had work for it (the handles' predictors: api_encode.cpp
-// ovtk_bpe).  A wrong guess costs one more round of launches (~0.1 ms), a needless launch a few microseconds: four calls without work
+// A run-time bool as a template argument: f(std::true_type{}) or f(std::false_type{}) -- both forms of whatever f launches are
+// instantiated, as the if / else pair it stands for would.
+template <class F>
+inline void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// Which kernels a fused encode call launches (RegexSplit [+] BPETokenizer: api_encode.cpp; the BERT splits + WordpieceTokenizer:
+// api_ops.cpp).  Filled once per call, before anything is launched; the run, its middle and every repeat of an attempt read this and
+// nothing else -- in particular not the two process-wide switches above, which plan_front() reads once.
+enum EncodeFront : int {
+    kFrontGeneric = 0,   // lookup_kernel<mode> alone, every row
+    kFrontTicketed,      // lookup_kernel<mode, true>: rows handed out rows_per_ticket at a time
+    kFrontSpan,          // lookup_span_kernel<scan, stage16>: several rows per scan block; it probes the memo for every piece
+    kFrontRows,          // lookup_rows_kernel<scan>: the row-per-scan kernel, a handle without a memo
+};
+struct EncodePlan {
+    int front = kFrontGeneric;
+    int scan = -1;               // kSpan* / kRows* of the front kernel (the kinds both enums have carry the same number); -1: the op has none
+    int mode = 0;                // EncodeMode of lookup_kernel -- the whole call, or the rows the front kernel leaves -- and of encode_small_kernel
+    const char* front_tag = "";  // the profiler's tags: the span / rows kernel,
+    const char* whole_tag = "";  // lookup_kernel where it is the call's first kernel,
+    const char* rest_tag = "";   // lookup_kernel behind the front kernel
+    bool small_ok = false;       // the one-launch form of a small batch may be taken (encode_small_kernel)
+    bool stage16 = false;        // the staging entries of the call are u16 (EncodeWork::stage16)
+    bool narrow_ids = false;     // every token id < 65536: merge_kernel / encode_small_kernel keep ids as u16 in LDS
+    bool stage_twice = false;    // staging room for the front kernel and the generic kernel behind it (RowsRun::start)
+    bool short_ok = false;       // the short path may be taken (span_kernel.hpp): the front kernel is lookup_span_kernel
+    int rows_per_ticket = 0;     // what ovtk_set_row_tickets() / ovtk_set_short_path() had set when the call started: the run and
+    int short_path_mode = 1;     // every repeat of an attempt keep to it
+    int blocks_per_cu = 6;       // the persistent grid: blocks per CU of the kernel whose residency the op asks for
+};
+// The front of a call and what follows from it.  scan: the op's scan for this call's split (-1: none -- pieces come in split);
+// has_memo: there is a memo for lookup_span_kernel to probe; ticketed_form: the op launches lookup_kernel<mode, true> under row
+// tickets (the fused WordPiece encode launches the plain form with rows_per_ticket set); small_form: it has a one-launch form.
+inline void plan_front(EncodePlan& p, int scan, bool has_memo, bool ticketed_form, bool small_form) {
+    p.rows_per_ticket = row_tickets().load(std::memory_order_relaxed);
+    p.short_path_mode = short_path_mode().load(std::memory_order_relaxed);
+    const bool tickets = p.rows_per_ticket != 0;
+    p.scan = scan;
+    p.front = tickets ? (ticketed_form ? kFrontTicketed : kFrontGeneric) : scan < 0 ? kFrontGeneric : has_memo ? kFrontSpan : kFrontRows;
+    p.small_ok = small_form && !tickets;
+    // (lookup_span_kernel in front of the generic kernel; as before the plan existed, the room is taken wherever the handle COULD take
+    // that front -- under row tickets too)
+    p.stage_twice = scan >= 0 && has_memo;
+    // The short path (span_kernel.hpp): where the call's first kernel is lookup_span_kernel, the kernels behind it are launched only when
+    // the handle's last calls had work for them.
+    p.short_ok = p.front == kFrontSpan && p.short_path_mode != 0;
+}
+
+// Calls for which a kernel of the middle is still launched after a call that had work for it (the handles' predictors, below).
+// A wrong guess costs one more round of launches (~0.1 ms), a needless launch a few microseconds: four calls without work
 // and the kernel is left out -- the driver's bench line (8 priming + 5 warm-up calls in front of 20 timed ones) then times the steady form.
 constexpr int kShortPathKeep = 4;
+// The short path's predictors of a handle (ovtk_bpe, ovtk_wordpiece): calls during which the kernels of the middle are still launched
+// whatever the last call said -- lookup_kernel<kFused> for left-over rows, merge_kernel / wordpiece_deferred_kernel for pieces in
+// neither table.  Set to kShortPathKeep by every call that had such rows / pieces, counted down by every call that had none; a new
+// handle's tables are empty: its first calls merge.
+struct ShortPathPredictor {
+    mutable std::atomic<int> expect_pending{0}, expect_merge{kShortPathKeep};
+    mutable std::atomic<int> last_unresolved{-1};   // pieces the last such call left for the deferred kernel (sizes its launch)
+    struct Guess {
+        bool pending, merge;
+        int64_t merge_hint;   // (< 0: unknown)
+    };
+    // What this call should expect.  has_store: the handle has a piece store -- without one every piece the memo lacks is merged.
+    Guess arm(bool has_store) const {
+        return Guess{expect_pending.load(std::memory_order_relaxed) > 0, expect_merge.load(std::memory_order_relaxed) > 0 || !has_store,
+                     has_store ? int64_t(last_unresolved.load(std::memory_order_relaxed)) : int64_t(-1)};
+    }
+    // The status block of the attempt that completed a run: the span kernel counted what the call's text left to the kernels of the middle.
+    void note(const RunStatus& st) const {
+        if (!st.short_path) return;
+        auto count = [](std::atomic<int>& expect, bool had_work) {
+            if (had_work) expect.store(kShortPathKeep, std::memory_order_relaxed);
+            else if (expect.load(std::memory_order_relaxed) > 0) expect.fetch_sub(1, std::memory_order_relaxed);
+        };
+        count(expect_pending, st.n_pending > 0);
+        if (st.short_path != 3) {   // (3: the long way, nothing was counted)
+            count(expect_merge, st.n_unresolved > 0);
+            last_unresolved.store(st.n_unresolved, std::memory_order_relaxed);
+        }
+    }
+};
 // ovtk_short_path_stats(): calls launched as span -> compact / of them, calls that needed no other kernel.
 struct ShortPathCounts { std::atomic<int64_t> tried{0}, exact{0}; };
 inline ShortPathCounts& short_path_counts() {
@@ -310,6 +406,16 @@ struct ovtk_pending {
 };
 namespace ovtk {
 
+// The first half of a call in two: start(p) launches into p.out / p.run; the pending call is the caller's only once that went well.
+template <class Start>
+inline int enqueue_pending(const ovtk_ragged_i32_out& out, ovtk_pending** pending, Start&& start) {
+    auto p = std::make_unique<ovtk_pending>();
+    p->out = out;
+    if (int rc = start(*p)) return rc;
+    *pending = p.release();
+    return OVTK_OK;
+}
+
 // Up to this many rows the last block of merge_kernel sums the row counts itself (one block reads 4 bytes per row);
 // larger batches keep the parallel count_scan_kernel.
 constexpr int kFoldTailRows = 1 << 18;
@@ -319,15 +425,42 @@ constexpr int kSmallRows = 256;
 constexpr int64_t kSmallChars = 64 << 10;
 
 
+// The middle of a fused encode behind the one-launch form: front kernel -> lookup_kernel for the rows it left -> the deferred kernel.
+// `k` holds the op's kernels (each translation unit instantiates its own and no others):
+//   k.front(ws, d_in, w1, grid1)      the plan's span / rows kernel
+//   k.lookup(ws, d_in, w, grid, tag)  lookup_kernel<plan.mode> (the ticketed form where the plan's front is that)
+//   k.deferred(ws, d_in, w)           what works through the deferred list: merge_kernel (+ exact_kernel), wordpiece_deferred_kernel
+template <class Kernels>
+inline void launch_middle(const EncodePlan& p, const Kernels& k, Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) {
+    if (p.front == kFrontSpan || p.front == kFrontRows) {
+        // several rows per scan block: lookup_span_kernel (it probes the memo for every piece: a handle without one -- cache_capacity = 0
+        // -- takes the row-per-scan kernel); whatever they leave (marked in row_used, listed in pending_rows) goes through the generic kernel
+        EncodeWork w1 = w;
+        const int grid1 = rows_grid(d_in.n_rows, grid, w1.rows_per_wave);
+        if (w.launch_mask & kLaunchSpan) k.front(ws, d_in, w1, grid1);   // (not in the short path's second set of launches: the span kernel has run)
+        // what it left: the generic kernel (it returns at once when nothing was left).  A smaller stand-by grid for handles whose last
+        // call left no row was measured: nothing gained on all-ASCII text (6.0 vs 6.2 us), and the rows that do turn up then wait for
+        // 64 blocks to walk every row's flag
+        EncodeWork w2 = w;
+        w2.only_pending = 1;
+        if (w.launch_mask & kLaunchPending) k.lookup(ws, d_in, w2, grid, p.rest_tag);
+    } else {
+        k.lookup(ws, d_in, w, grid, p.whole_tag);
+    }
+    if (!(w.launch_mask & kLaunchMerge)) return;   // (the short path: nothing is expected to be left for the deferred kernel)
+    k.deferred(ws, d_in, w);
+}
+
 template <class Middle>
 class RowsRun final : public PendingRun {
 public:
+    // plan: the launch plan of a fused encode, whose middle's first kernel validates the offsets and takes its staging from bump
+    // allocators itself and whose last kernel finishes the row scan while the batch is small; nullptr: an op with a prep launch.
     RowsRun(int device, const char* op, const ovtk_ragged_strings* in, const uint8_t* skips, int mul,
-            const ovtk_ragged_i32_out* out, int mem, hipStream_t s, Middle middle, bool self_alloc, int blocks_per_cu,
-            bool tail_in_middle)
+            const ovtk_ragged_i32_out* out, int mem, hipStream_t s, Middle middle, const EncodePlan* plan)
         : device_(device), op_(op), in_(*in), skips_(skips), mul_(mul), out_(*out), mem_(mem), in_mem_(mem), s_(s),
-          middle_(std::move(middle)), self_alloc_(self_alloc), blocks_per_cu_(blocks_per_cu), ws_(device),
-          fold_tail_(tail_in_middle) {}
+          middle_(std::move(middle)), self_alloc_(plan != nullptr), plan_(plan ? *plan : EncodePlan{}), ws_(device),
+          fold_tail_(plan != nullptr), small_ok_(plan_.small_ok) {}
 
     // The input tensors live in device memory whatever `mem` says about the outputs (pieces produced on the device by
     // a preceding split; `keep` = what owns them, released with this run).
@@ -335,8 +468,6 @@ public:
         in_mem_ = OVTK_MEM_DEVICE;
         keep_ = std::move(keep);
     }
-    // The middle knows the one-launch form of a small batch (EncodeWork::small, encode_small_kernel).
-    void enable_small() { small_ok_ = true; }
     // Called with the status block of the attempt that completed the run (finish(), the caller's thread).
     void on_status(std::function<void(const RunStatus&)> f) { on_status_ = std::move(f); }
     // Kernels of another workspace run in front of this run's on the same stream (a split into device buffers): once this
@@ -345,22 +476,16 @@ public:
     // Asked once this run's event has completed, before its own status is looked at: what a stage in front of it (another
     // workspace's kernels on the same stream) has to say; non-zero ends finish() with that code.
     void front_check(std::function<int()> f) { front_check_ = std::move(f); }
-    // The middle's first kernel is lookup_span_kernel and does the middle's bookkeeping itself (EncodeWork::span_sums, span_kernel.hpp
-    // "the short path"); of the kernels behind it only those are launched that the handle expects to find work -- lookup_kernel<kFused>
-    // for left-over rows, merge_kernel / wordpiece_deferred_kernel for pieces that are in neither table.  What was left out and was
-    // needed after all follows from finish() (compact_kernel wrote nothing then).
-    // merge_hint: pieces the handle's last call left for merge_kernel / wordpiece_deferred_kernel (< 0: unknown) -- sizes that launch.
-    void enable_short_path(bool expect_pending, bool expect_merge, int64_t merge_hint) {
-        short_ok_ = true;
-        expect_pending_ = expect_pending;
-        expect_merge_ = expect_merge;
-        merge_hint_ = merge_hint;
+    // The plan's short path (EncodePlan::short_ok): the middle's first kernel is lookup_span_kernel and does the middle's bookkeeping itself
+    // (EncodeWork::span_sums, span_kernel.hpp "the short path"); of the kernels behind it only those are launched that the handle expects
+    // to find work -- lookup_kernel<kFused> for left-over rows, merge_kernel / wordpiece_deferred_kernel for pieces that are in neither
+    // table.  What was left out and was needed after all follows from finish() (compact_kernel wrote nothing then).
+    // guess.merge_hint: pieces the handle's last call left for merge_kernel / wordpiece_deferred_kernel -- sizes that launch.
+    void expect(const ShortPathPredictor::Guess& guess) {
+        expect_pending_ = guess.pending;
+        expect_merge_ = guess.merge;
+        merge_hint_ = guess.merge_hint;
     }
-    void enable_stage16() { stage16_ = true; }   // the middle's kernels write / read the staging entries as u16 (EncodeWork::stage16)
-    // The middle's first kernel takes staging for ALL its rows before it knows which of them it will leave to the kernel behind it
-    // (lookup_span_kernel: one reservation per wave), and that kernel takes its own: room for both, or every call with left-over
-    // rows would overflow, grow and run twice.
-    void stage_twice() { stage_twice_ = true; }
     // The result leaves in the row-shard exchange's wire form (device memory) instead of begins / ends / ids.
     void output_to_wire(const WireSink& wire) {
         wire_ = wire;
@@ -401,9 +526,12 @@ public:
                 if (int rc = out_target(ws_->out_c, out_.data, size_t(out_.data_capacity) * 4, mem_, &d_ids_)) return rc;
             }
         }
-        grid_ = grid_rows(device_, n_rows_, blocks_per_cu_);
+        grid_ = grid_rows(device_, n_rows_, plan_.blocks_per_cu);
         n_tiles_ = (n_rows_ + kRowTile - 1) / kRowTile;
-        if (stage_twice_) stage_cap_ = std::min<int64_t>(stage_cap_ * 2, INT32_MAX - 1);
+        // The middle's first kernel takes staging for ALL its rows before it knows which of them it will leave to the kernel behind it
+        // (lookup_span_kernel: one reservation per wave), and that kernel takes its own: room for both, or every call with left-over
+        // rows would overflow, grow and run twice.
+        if (plan_.stage_twice) stage_cap_ = std::min<int64_t>(stage_cap_ * 2, INT32_MAX - 1);
         if (self_alloc_) {  // every wave may leave one chunk partly unused -- the waves that are LAUNCHED: lookup_rows_kernel's grid grows
                            // beyond the persistent one when a wave would own more than 64 rows (rows_grid(); ADVICE r04: with the persistent
                            // grid's slack a batch of a million short rows overflowed at its first attempt and ran twice)
@@ -525,9 +653,9 @@ private:
         size_t status_bytes = sizeof(RunStatus) + (fold ? size_t(n_tiles_) * 4 + 16 : 0);  // + tile_cnt, zeroed with the status (+ slack: compact_kernel reads it 16 bytes at a time)
         // the short path (span_kernel.hpp): tile_cnt is summed by the lookup kernels' waves, every wave of compact_kernel sums the tiles in
         // front of its own
-        const int sp_mode = short_path_mode().load(std::memory_order_relaxed);
-        small_ = small_ && !(short_ok_ && sp_mode == 2);   // (mode 2: tests drive it with small batches)
-        const bool span_sums = short_ok_ && !small_ && self_alloc_ && fold && sp_mode != 0 && !force_long_;
+        const int sp_mode = plan_.short_path_mode;
+        small_ = small_ && !(plan_.short_ok && sp_mode == 2);   // (mode 2: tests drive it with small batches)
+        const bool span_sums = plan_.short_ok && !small_ && fold && !force_long_;
         const size_t status_stride = (status_bytes + 255) & ~size_t(255);   // two blocks: this call's, and the one compact_kernel zeroes for the next
         e = e ? e : ws.status.ensure(2 * status_stride);
         if (fold) e = e ? e : ws.gen[4].ensure(size_t(n_rows_) * 4);
@@ -541,7 +669,7 @@ private:
         w.row_emit = fold ? ws.gen[4].as<int32_t>() : nullptr;
         w.pending_rows = self_alloc_ ? ws.gen[5].as<int32_t>() : nullptr;
         w.out_cap = out_.data_capacity;
-        w.rows_per_ticket = self_alloc_ ? row_tickets().load(std::memory_order_relaxed) : 0;
+        w.rows_per_ticket = plan_.rows_per_ticket;
         w.wave_off = self_alloc_ ? nullptr : ws.wave_off.as<long long>();
         w.stage_region = int32_t(stage_cap_ / kShards);
         w.row_stage = ws.row_stage.as<int32_t>();
@@ -550,7 +678,7 @@ private:
         w.tile_off = ws.tiles.as<long long>();
         w.stage = ws.stage.as<int32_t>();
         w.stage_cap = int32_t(stage_cap_);
-        w.stage16 = stage16_ ? 1 : 0;
+        w.stage16 = plan_.stage16 ? 1 : 0;
         w.deferred = ws.deferred.as<DeferredPiece>();
         w.shard_cap = int32_t(std::min<int64_t>(shard_cap_, INT32_MAX / kShards));
         w.exact = ws.exact.as<ExactPiece>();
@@ -663,14 +791,14 @@ private:
         const long long units = ((long long)n_rows_ + kCompactRows - 1) / kCompactRows * split;
         const int cgrid = int(std::max<long long>(1, std::min<long long>((units + kWavesPerBlock - 1) / kWavesPerBlock, (long long)device_cu_count(device_) * 16)));
         const RaggedSink rsink{d_ids_, d_begins_, d_ends_};
-        if (dense_on_) {
-            OVTK_LAUNCH(ws.marks, "row_width", row_width_kernel, std::min(64, (n_rows_ + kBlockThreads - 1) / kBlockThreads), kBlockThreads, s_, n_rows_, w, dense_);
-            if (stage16_) OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<DenseSink, true>), cgrid, kBlockThreads, s_, n_rows_, w, dense_);
-            else OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<DenseSink, false>), cgrid, kBlockThreads, s_, n_rows_, w, dense_);
-        } else if (wire_.hdr && stage16_) OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<WireSink, true>), cgrid, kBlockThreads, s_, n_rows_, w, wire_);
-        else if (wire_.hdr) OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<WireSink, false>), cgrid, kBlockThreads, s_, n_rows_, w, wire_);
-        else if (stage16_) OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<RaggedSink, true>), cgrid, kBlockThreads, s_, n_rows_, w, rsink);
-        else OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<RaggedSink, false>), cgrid, kBlockThreads, s_, n_rows_, w, rsink);
+        with_bool(plan_.stage16, [&](auto s16) {
+            constexpr bool S16 = decltype(s16)::value;
+            if (dense_on_) {
+                OVTK_LAUNCH(ws.marks, "row_width", row_width_kernel, std::min(64, (n_rows_ + kBlockThreads - 1) / kBlockThreads), kBlockThreads, s_, n_rows_, w, dense_);
+                OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<DenseSink, S16>), cgrid, kBlockThreads, s_, n_rows_, w, dense_);
+            } else if (wire_.hdr) OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<WireSink, S16>), cgrid, kBlockThreads, s_, n_rows_, w, wire_);
+            else OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<RaggedSink, S16>), cgrid, kBlockThreads, s_, n_rows_, w, rsink);
+        });
         // (the other status block is clean for the next lease of this workspace once this call's compact_kernel has RUN: noted in
         // finish(), after the event -- ADVICE r04: noted here, a run that was dropped without finish(), or whose launch failed
         // afterwards, left the next lease without its memset)
@@ -696,12 +824,11 @@ private:
     hipStream_t s_;
     Middle middle_;
     bool self_alloc_;
-    int blocks_per_cu_;
+    EncodePlan plan_;        // (default-constructed for the ops without one: no tickets, no short path, i32 staging, 6 blocks per CU)
     WorkspaceLease ws_;
     bool fold_tail_;  // the middle's last kernel finishes the row scan itself (BPE: merge_kernel) while the batch is small
-    bool small_ok_ = false, small_ = false;
-    bool stage16_ = false, stage_twice_ = false;
-    bool short_ok_ = false, expect_pending_ = false, expect_merge_ = true, force_long_ = false;
+    bool small_ok_ = false, small_ = false;   // small_ok_: the plan's, unless the result leaves as a wire or dense
+    bool expect_pending_ = false, expect_merge_ = true, force_long_ = false;
     int64_t merge_hint_ = -1;
     int phase_ = 0;          // 1: the attempt in flight is the short path's first set of launches; 2: what it had left out was launched after all
     EncodeWork w_{};         // the attempt's work description (phase 2 launches with it)
@@ -724,19 +851,15 @@ private:
 template <class Middle>
 std::unique_ptr<RowsRun<std::decay_t<Middle>>> make_rows_run(int device, const char* op, const ovtk_ragged_strings* in,
                                                              const uint8_t* skips, int mul, const ovtk_ragged_i32_out* out, int mem,
-                                                             hipStream_t s, Middle&& middle, bool self_alloc = false,
-                                                             int blocks_per_cu = 6, bool tail_in_middle = false) {
-    return std::make_unique<RowsRun<std::decay_t<Middle>>>(device, op, in, skips, mul, out, mem, s, std::forward<Middle>(middle),
-                                                           self_alloc, blocks_per_cu, tail_in_middle);
+                                                             hipStream_t s, Middle&& middle, const EncodePlan* plan = nullptr) {
+    return std::make_unique<RowsRun<std::decay_t<Middle>>>(device, op, in, skips, mul, out, mem, s, std::forward<Middle>(middle), plan);
 }
 
 // The synchronous form every *_run entry point uses.  `middle` is copied: capture by value.
 template <class Middle>
 int run_rows_to_ids(int device, const char* op, const ovtk_ragged_strings* in, const uint8_t* skips, int mul,
-                    ovtk_ragged_i32_out* out, int mem, hipStream_t s, Middle&& middle, bool self_alloc = false,
-                    int blocks_per_cu = 6, bool tail_in_middle = false) {
-    auto run = make_rows_run(device, op, in, skips, mul, out, mem, s, std::forward<Middle>(middle), self_alloc, blocks_per_cu,
-                             tail_in_middle);
+                    ovtk_ragged_i32_out* out, int mem, hipStream_t s, Middle&& middle) {
+    auto run = make_rows_run(device, op, in, skips, mul, out, mem, s, std::forward<Middle>(middle));
     if (int rc = run->start()) return rc;
     return run->finish(out);
 }

@@ -108,16 +108,12 @@ struct ovtk_bpe {
     // calls that still leave the piece store out: set to 32 after four calls in a row in which fewer than one probe in eight
     // hit (then the store is asked again, and so on -- text changes)
     mutable std::atomic<int> store_pause{0}, store_low{0};  // store_low: calls in a row with that little use of it
-    // The short path (span_kernel.hpp): calls during which the kernels of the middle are still launched whatever the last call said --
-    // lookup_kernel<kFused> for left-over rows, merge_kernel for pieces in neither table.  Set to kShortPathKeep by every call that had such
-    // rows / pieces, counted down by every call that had none; a new handle's tables are empty: its first calls merge.
-    mutable std::atomic<int> expect_pending{0}, expect_merge{kShortPathKeep};
-    mutable std::atomic<int> last_unresolved{-1};   // pieces the last such call left for merge_kernel (sizes its launch)
+    ShortPathPredictor predict;   // the short path (span_kernel.hpp): which kernels of the middle a call still launches
 };
 
 namespace {
 int run_encode(const ovtk_regex_split* split, const ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
-               ovtk_ragged_i32_out* out, int mem, void* stream);
+               ovtk_ragged_i32_out* out, int mem, void* stream, const ovtk_special_tokens_split* special = nullptr);
 
 // The piece memo (tables.hpp PieceEntry): BPE(t) for every vocabulary token t used as a whole piece, computed by the
 // device BPE itself -- the handle (still without memo) encodes its own vocabulary, one token per row -- plus, filled
@@ -620,43 +616,71 @@ struct SparseFin {   // total -> status->n_out (special_sparse_kernel used the w
         if (total > cap) atomicOr(&status->flags, kFlagOutCapacity);
     }
 };
+// What the one-pass split stages leave in their workspace: every row's strings in a region of its own inside buffers of the reference's
+// capacity (gen[2..4]), the rows' begins / ends pointing there (gen[0..1]), counters and flags in the status block.
+struct SparseStage {
+    int32_t *rb = nullptr, *re = nullptr, *b = nullptr, *e = nullptr;
+    uint8_t* sk = nullptr;
+    RunStatus* st = nullptr;
+    long long cap = 0;   // entries of b / e / sk
+};
+// status: the stage is one of the one-pass forms below, which report through a status block of their own (zeroed here)
+int sparse_buffers(Workspace& sw, int n_rows, long long cap, bool skips, bool status, hipStream_t s, SparseStage& o) {
+    int e = 0;
+    e = e ? e : sw.gen[0].ensure(size_t(n_rows) * 4);
+    e = e ? e : sw.gen[1].ensure(size_t(n_rows) * 4);
+    e = e ? e : sw.gen[2].ensure(size_t(cap) * 4);
+    e = e ? e : sw.gen[3].ensure(size_t(cap) * 4);
+    if (skips) e = e ? e : sw.gen[4].ensure(size_t(cap));
+    if (status) e = e ? e : sw.status.ensure(sizeof(RunStatus));
+    if (e) return e;
+    o = SparseStage{sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(), sw.gen[2].as<int32_t>(), sw.gen[3].as<int32_t>(),
+                    skips ? sw.gen[4].as<uint8_t>() : nullptr, status ? sw.status.as<RunStatus>() : nullptr, cap};
+    if (status) OVTK_HIP(hipMemsetAsync(o.st, 0, sizeof(RunStatus), s));
+    return OVTK_OK;
+}
+// The compiled DFA in one pass (regex_sparse_kernel, regex_device.hpp: a lane per row, a character per turn): nothing is counted,
+// the host does not wait.  (A row of bad offsets has begin -1 / end 0 there.)  Used by the fused encode and by the op alone.
+int regex_sparse_stage(const ovtk_regex_split* h, Workspace& sw, const RowsIn& d_in, hipStream_t s, bool skips, SparseStage& o) {
+    const long long cap = (long long)d_in.n_chars + d_in.n_strings;   // src/regex_split.cpp:182
+    if (int rc = sparse_buffers(sw, d_in.n_rows, cap, skips, /*status=*/true, s, o)) return rc;
+    const int lane_grid = (d_in.n_rows + kBlockThreads - 1) / kBlockThreads;
+    [[maybe_unused]] const RegexSparseLds lay = regex_sparse_layout(h->regex.n_states * h->regex.n_syms, h->regex.cp_blocks_bytes);
+    note_launch(sw.marks, s);
+    Profiler& pf = Profiler::get();
+    if (pf.enabled()) pf.begin("regex_split", s, sw.marks);
+    with_bool(h->mode == 1 && h->max_splits == -1, [&](auto isolate) {
+        hipLaunchKernelGGL(regex_sparse_kernel<decltype(isolate)::value>, dim3(lane_grid), dim3(kBlockThreads), size_t(lay.total), s, d_in, h->regex, o.st,
+                           cap, o.rb, o.re, o.b, o.e, o.sk);
+    });
+    if (pf.enabled()) pf.end(s, sw.marks);
+    return OVTK_OK;
+}
+// SpecialTokensSplit in one pass over the text (special_sparse_kernel: a sweep of the text for the tokens' first bytes, only the rows in
+// which one turns up are walked; a wave per 64 rows, every wave's strings in a region of their own): entry `row` for the rows of at most
+// one string, behind the n_rows entries for the others.  Used by the fused encode and by the op alone.
+int special_sparse_stage(const ovtk_special_tokens_split* h, Workspace& sw, const RowsIn& d_in, hipStream_t s, SparseStage& o) {
+    const long long cap_extra = (long long)d_in.n_chars + d_in.n_strings;   // special_tokens_split.cpp:88-92, + skipped empty strings
+    if (int rc = sparse_buffers(sw, d_in.n_rows, d_in.n_rows + cap_extra, /*skips=*/true, /*status=*/true, s, o)) return rc;
+    OVTK_LAUNCH(sw.marks, "special_split", special_sparse_kernel, (d_in.n_rows + kWave - 1) / kWave, kBlockThreads, s, d_in, h->dev, o.st, cap_extra, o.rb,
+                o.re, o.b, o.e, o.sk);
+    return OVTK_OK;
+}
+
 // RegexSplit, the op alone, for a COMPILED pattern (the DFA): regex_sparse_kernel -- the fused encode's one-pass form, a lane per row, a
 // character per turn -- into buffers of the reference's capacity, the scan of the rows' counts, the gather.  Until round 6 the automaton ran
 // twice (regex_split_kernel<0 / 1>, split_on_device).  The hand-written scanners keep their count and write passes.
 int regex_one_pass(const ovtk_regex_split* h, Workspace& sw, const RowsIn& d_in, hipStream_t s, int32_t* d_rb, int32_t* d_re, int32_t* d_b,
                    int32_t* d_e, uint8_t* d_sk, long long capacity) {
     const int n_rows = d_in.n_rows;
-    const long long cap = (long long)d_in.n_chars + d_in.n_strings;   // src/regex_split.cpp:182
-    int e = 0;
-    e = e ? e : sw.gen[0].ensure(size_t(n_rows) * 4);
-    e = e ? e : sw.gen[1].ensure(size_t(n_rows) * 4);
-    e = e ? e : sw.gen[2].ensure(size_t(cap) * 4);
-    e = e ? e : sw.gen[3].ensure(size_t(cap) * 4);
-    e = e ? e : sw.gen[4].ensure(size_t(cap));
-    e = e ? e : sw.tiles.ensure(scan_tiles_bytes(n_rows));
-    e = e ? e : sw.status.ensure(sizeof(RunStatus));
-    if (e) return e;
-    RunStatus* st = sw.status.as<RunStatus>();
-    OVTK_HIP(hipMemsetAsync(st, 0, sizeof(RunStatus), s));
-    int32_t *t_rb = sw.gen[0].as<int32_t>(), *t_re = sw.gen[1].as<int32_t>(), *t_b = sw.gen[2].as<int32_t>(), *t_e = sw.gen[3].as<int32_t>();
-    uint8_t* t_sk = sw.gen[4].as<uint8_t>();
-    const int lane_grid = (n_rows + kBlockThreads - 1) / kBlockThreads;
-    const RegexSparseLds lay = regex_sparse_layout(h->regex.n_states * h->regex.n_syms, h->regex.cp_blocks_bytes);
-    note_launch(sw.marks, s);
-    Profiler& pf = Profiler::get();
-    if (pf.enabled()) pf.begin("regex_split", s, sw.marks);
-    if (h->mode == 1 && h->max_splits == -1)
-        hipLaunchKernelGGL(regex_sparse_kernel<true>, dim3(lane_grid), dim3(kBlockThreads), size_t(lay.total), s, d_in, h->regex, st, cap, t_rb, t_re, t_b, t_e,
-                           t_sk);
-    else
-        hipLaunchKernelGGL(regex_sparse_kernel<false>, dim3(lane_grid), dim3(kBlockThreads), size_t(lay.total), s, d_in, h->regex, st, cap, t_rb, t_re, t_b, t_e,
-                           t_sk);
-    if (pf.enabled()) pf.end(s, sw.marks);
-    // (a row of bad offsets has begin -1 / end 0 there: SparseBadRows turns that into the range error the count pass used to raise)
-    launch_scan(sw.marks, "regex_split", s, (long long)n_rows, SparseRowLen{t_rb, t_re, st}, SparseRowOffsets{d_rb, d_re}, SparseFin{st, capacity},
-                sw.tiles.as<long long>(), st, kFlagOutCapacity | kFlagRange);
-    OVTK_LAUNCH(sw.marks, "regex_split", sparse_gather_kernel, grid_lookup(h->device, n_rows), kBlockThreads, s, n_rows, (const int32_t*)t_rb, (const int32_t*)t_b,
-                (const int32_t*)t_e, (const uint8_t*)t_sk, (const int32_t*)d_rb, (const int32_t*)d_re, d_b, d_e, d_sk, (const RunStatus*)st,
+    if (int rc = sw.tiles.ensure(scan_tiles_bytes(n_rows))) return rc;
+    SparseStage t;
+    if (int rc = regex_sparse_stage(h, sw, d_in, s, /*skips=*/true, t)) return rc;
+    // (a row of bad offsets has begin -1 / end 0 there: SparseRowLen turns that into the range error the count pass used to raise)
+    launch_scan(sw.marks, "regex_split", s, (long long)n_rows, SparseRowLen{t.rb, t.re, t.st}, SparseRowOffsets{d_rb, d_re}, SparseFin{t.st, capacity},
+                sw.tiles.as<long long>(), t.st, kFlagOutCapacity | kFlagRange);
+    OVTK_LAUNCH(sw.marks, "regex_split", sparse_gather_kernel, grid_lookup(h->device, n_rows), kBlockThreads, s, n_rows, (const int32_t*)t.rb, (const int32_t*)t.b,
+                (const int32_t*)t.e, (const uint8_t*)t.sk, (const int32_t*)d_rb, (const int32_t*)d_re, d_b, d_e, d_sk, (const RunStatus*)t.st,
                 uint32_t(kFlagOutCapacity | kFlagRange));
     return OVTK_OK;
 }
@@ -743,25 +767,11 @@ int split_one_pass(const ovtk_regex_split* h, Workspace& sw, const RowsIn& d_in,
 int special_one_pass(const ovtk_special_tokens_split* h, Workspace& sw, const RowsIn& d_in, hipStream_t s, int32_t* d_rb, int32_t* d_re,
                      int32_t* d_b, int32_t* d_e, uint8_t* d_sk, long long capacity) {
     const int n_rows = d_in.n_rows;
-    const long long cap_extra = (long long)d_in.n_chars + d_in.n_strings;   // special_tokens_split.cpp:88-92, + skipped empty strings
-    const long long cap = n_rows + cap_extra;
-    int e = 0;
-    e = e ? e : sw.gen[0].ensure(size_t(n_rows) * 4);
-    e = e ? e : sw.gen[1].ensure(size_t(n_rows) * 4);
-    e = e ? e : sw.gen[2].ensure(size_t(cap) * 4);
-    e = e ? e : sw.gen[3].ensure(size_t(cap) * 4);
-    e = e ? e : sw.gen[4].ensure(size_t(cap));
-    e = e ? e : sw.tiles.ensure(scan_tiles_bytes(n_rows));
-    e = e ? e : sw.status.ensure(sizeof(RunStatus));
-    if (e) return e;
-    RunStatus* st = sw.status.as<RunStatus>();
-    OVTK_HIP(hipMemsetAsync(st, 0, sizeof(RunStatus), s));
-    int32_t *t_rb = sw.gen[0].as<int32_t>(), *t_re = sw.gen[1].as<int32_t>(), *t_b = sw.gen[2].as<int32_t>(), *t_e = sw.gen[3].as<int32_t>();
-    uint8_t* t_sk = sw.gen[4].as<uint8_t>();
-    OVTK_LAUNCH(sw.marks, "special_split", special_sparse_kernel, (n_rows + kWave - 1) / kWave, kBlockThreads, s, d_in, h->dev, st, cap_extra, t_rb, t_re, t_b,
-                t_e, t_sk);
-    launch_scan(sw.marks, "special_split", s, (long long)n_rows, SparseRowLen{t_rb, t_re, nullptr}, SparseRowGather{t_rb, t_b, t_e, t_sk, d_rb, d_re, d_b, d_e, d_sk},
-                SparseFin{st, capacity}, sw.tiles.as<long long>(), st, kFlagOutCapacity | kFlagRange);
+    if (int rc = sw.tiles.ensure(scan_tiles_bytes(n_rows))) return rc;
+    SparseStage t;
+    if (int rc = special_sparse_stage(h, sw, d_in, s, t)) return rc;
+    launch_scan(sw.marks, "special_split", s, (long long)n_rows, SparseRowLen{t.rb, t.re, nullptr}, SparseRowGather{t.rb, t.b, t.e, t.sk, d_rb, d_re, d_b, d_e, d_sk},
+                SparseFin{t.st, capacity}, sw.tiles.as<long long>(), t.st, kFlagOutCapacity | kFlagRange);
     return OVTK_OK;
 }
 
@@ -795,6 +805,144 @@ int special_on_device(const ovtk_special_tokens_split* h, Workspace& sw, const R
     return OVTK_OK;
 }
 
+// The scan lookup_span_kernel / lookup_rows_kernel has for a split the lookup kernels run themselves (fusable()), and the lookup_kernel mode.
+int scan_of(const ovtk_regex_split* split) {
+    if (!split) return -1;
+    if (split->dev.kind == kSplitLlama3) return kSpanLlama3;
+    if (split->dev.family != kFamNone) return split->dev.family == kFamDs3 ? kSpanDs3 : kSpanO200k;
+    return split->dev.kind == kSplitGpt2Digits ? kSpanGpt2Digits : kSpanGpt2;
+}
+int mode_of(const ovtk_regex_split* split) {
+    if (!split) return kPieces;
+    return split->dev.kind == kSplitLlama3 ? kFusedLlama3 : split->dev.family != kFamNone ? kFusedSeq : kFused;
+}
+static_assert(int(kSpanGpt2) == int(kRowsGpt2) && int(kSpanGpt2Digits) == int(kRowsGpt2Digits) && int(kSpanLlama3) == int(kRowsLlama3),
+              "EncodePlan::scan numbers the span and the rows kernel's scans alike");
+
+// The launch plan of a BPE encode: `split` is what the lookup kernels run themselves (nullptr: `in` holds pieces), T this call's tables.
+EncodePlan plan_encode(const ovtk_regex_split* split, const ovtk_bpe* bpe, const BpeDev& T) {
+    EncodePlan p;
+    p.mode = mode_of(split);
+    p.front_tag = T.pieces.slots ? "lookup_span" : "lookup_rows";
+    p.whole_tag = split ? "lookup_fused" : "lookup_pieces";
+    p.rest_tag = "lookup_fused";
+    p.stage16 = bpe->stage16;
+    p.narrow_ids = bpe->narrow_ids;
+    plan_front(p, scan_of(split), T.pieces.slots != nullptr, /*ticketed_form=*/true, /*small_form=*/true);
+    // The kernel whose residency sizes the persistent grid: one per family of fronts, as measured -- the span kernel's where the family has
+    // one and rows are not handed out by tickets (GPT-2's also in front of the rows kernel), else the family's lookup_kernel.
+    const bool tickets = p.front == kFrontTicketed;
+    switch (p.mode) {
+    case kPieces: p.blocks_per_cu = resident_blocks_per_cu(lookup_kernel<kPieces>); break;
+    case kFusedSeq:
+        p.blocks_per_cu = !tickets ? resident_blocks_per_cu(lookup_span_kernel<kSpanO200k, false>) : resident_blocks_per_cu(lookup_kernel<kFusedSeq>);
+        break;
+    case kFusedLlama3:
+        p.blocks_per_cu = p.front == kFrontSpan ? resident_blocks_per_cu(lookup_span_kernel<kSpanLlama3, false>) : resident_blocks_per_cu(lookup_kernel<kFusedLlama3>);
+        break;
+    default:
+        p.blocks_per_cu = !tickets ? resident_blocks_per_cu(lookup_span_kernel<kSpanGpt2, true>, 6) : resident_blocks_per_cu(lookup_kernel<kFused>);
+    }
+    return p;
+}
+
+// EncodePlan::mode as a template argument: f(std::integral_constant<int, MODE>{}).
+template <class F>
+void with_mode(int mode, F&& f) {
+    switch (mode) {
+    case kFusedLlama3: f(std::integral_constant<int, kFusedLlama3>{}); break;
+    case kFusedSeq: f(std::integral_constant<int, kFusedSeq>{}); break;
+    case kFused: f(std::integral_constant<int, kFused>{}); break;
+    default: f(std::integral_constant<int, kPieces>{});
+    }
+}
+
+// The kernels of a BPE encode for launch_middle() (api_common.hpp) and the one-launch form.
+struct BpeKernels {
+    EncodePlan plan;
+    SplitDev sd;   // (SplitDev{} where the pieces come in split)
+    BpeDev T;
+    int device;
+    hipStream_t s;
+
+    // the whole call in one launch of one block
+    void small(Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) const {
+        with_mode(plan.mode, [&](auto mode) {
+            with_bool(plan.narrow_ids, [&](auto narrow) {
+                OVTK_LAUNCH(ws.marks, "encode_small", (encode_small_kernel<decltype(mode)::value, decltype(narrow)::value>), grid, kBlockThreads, s, d_in, sd, T, w);
+            });
+        });
+    }
+    // Llama-3: the rule algebra on bit masks (lookup_span_kernel<kSpanLlama3>, span_l3.hpp; round 4's row-per-scan kernel stays for handles
+    // without a memo).  DeepSeek-V3's pattern, o200k_base: the scan of span_fam.hpp on the span kernel's blocks; the rows it leaves (several
+    // strings, skipped ones) are matched literally, a lane per row's window.
+    template <int SCAN>
+    void span(Workspace& ws, const RowsIn& d_in, const EncodeWork& w1, int grid1) const {
+        with_bool(w1.stage16 != 0, [&](auto s16) {
+            OVTK_LAUNCH(ws.marks, plan.front_tag, (lookup_span_kernel<SCAN, decltype(s16)::value>), grid1, kBlockThreads, s, d_in, sd, T, w1);
+        });
+    }
+    void front(Workspace& ws, const RowsIn& d_in, const EncodeWork& w1, int grid1) const {
+        if (plan.front == kFrontSpan) {
+            switch (plan.scan) {
+            case kSpanLlama3: span<kSpanLlama3>(ws, d_in, w1, grid1); break;
+            case kSpanDs3: span<kSpanDs3>(ws, d_in, w1, grid1); break;
+            case kSpanO200k: span<kSpanO200k>(ws, d_in, w1, grid1); break;
+            case kSpanGpt2Digits: span<kSpanGpt2Digits>(ws, d_in, w1, grid1); break;
+            default: span<kSpanGpt2>(ws, d_in, w1, grid1);
+            }
+        } else if (plan.scan == kRowsLlama3)
+            OVTK_LAUNCH(ws.marks, plan.front_tag, lookup_rows_kernel<kRowsLlama3>, grid1, kBlockThreads, s, d_in, sd, T, w1);
+        else if (plan.scan == kRowsGpt2Digits)
+            OVTK_LAUNCH(ws.marks, plan.front_tag, lookup_rows_kernel<kRowsGpt2Digits>, grid1, kBlockThreads, s, d_in, sd, T, w1);
+        else
+            OVTK_LAUNCH(ws.marks, plan.front_tag, lookup_rows_kernel<kRowsGpt2>, grid1, kBlockThreads, s, d_in, sd, T, w1);
+    }
+    void lookup(Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid, const char* tag) const {
+        with_mode(plan.mode, [&](auto mode) {
+            with_bool(plan.front == kFrontTicketed, [&](auto tickets) {
+                OVTK_LAUNCH(ws.marks, tag, (lookup_kernel<decltype(mode)::value, decltype(tickets)::value>), grid, kBlockThreads, s, d_in, sd, T, w);
+            });
+        });
+    }
+    void deferred(Workspace& ws, const RowsIn& d_in, const EncodeWork& w) const {
+        const int tail_rows = w.fold_tail ? d_in.n_rows : 0;
+        with_bool(plan.narrow_ids, [&](auto narrow) {
+            constexpr bool N = decltype(narrow)::value;
+            static const int per_cu = resident_blocks_per_cu(merge_kernel<N>);
+            OVTK_LAUNCH(ws.marks, "bpe_merge", merge_kernel<N>,
+                        dim3(kShards, grid_deferred_hinted(grid_deferred_per_shard(d_in.n_chars, d_in.n_strings, device_cu_count(device) * per_cu / kShards), w.span_sums, w.merge_hint)),
+                        kBlockThreads, s, d_in, T, w, tail_rows, w.out_cap);
+        });
+        if (!w.fold_tail) OVTK_LAUNCH(ws.marks, "bpe_exact", exact_kernel, 64, kBlockThreads, s, d_in, T, w);
+    }
+};
+
+// What the stages in front of an encode (other workspaces' kernels on the same stream) have to say once the run's event has completed.
+int check_front_stages(const WorkspaceLease* special_ws, const WorkspaceLease* sparse_ws) {
+    if (special_ws) {
+        const RunStatus& st = *special_ws->ws->host_status;
+        if (st.flags & kFlagRange) return set_error(OVTK_E_RANGE, "input begins/ends index outside their tensors");
+        if (st.flags & kFlagOutCapacity) return set_error(OVTK_E_CAPACITY, "SpecialTokensSplit: more strings than the reference's capacity");
+    }
+    if (sparse_ws && (sparse_ws->ws->host_status->flags & kFlagOutCapacity))
+        return set_error(OVTK_E_CAPACITY, "RegexSplit: the strings overlap -- their pieces need more room than the reference's n_chars + n_strings "
+                                          "(regex_split.cpp:182)");
+    return OVTK_OK;
+}
+
+// What the store did for a call decides whether the next ones ask it at all: set to pause for 32 calls after four calls in a row in
+// which fewer than one probe in eight hit.
+void note_store_use(const ovtk_bpe* bpe, const RunStatus& st) {
+    if (st.n_store_probe < 256) return;   // (counted by one wave in 64)
+    // (a cold store misses everything too: only a run of such calls says that the text is the reason)
+    if (st.n_store_hit * 8 >= st.n_store_probe) bpe->store_low.store(0, std::memory_order_relaxed);
+    else if (bpe->store_low.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
+        bpe->store_low.store(0, std::memory_order_relaxed);
+        bpe->store_pause.store(32, std::memory_order_relaxed);
+    }
+}
+
 // RegexSplit [+] BPETokenizer.  split == nullptr: `in` already holds pieces (the BPETokenizer op).
 // Launches the kernels; `run` stays empty when the result was complete without any (empty batches).
 int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
@@ -814,19 +962,9 @@ int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ov
     out->n_data = 0;
     out->n_rows = in->n_rows;
     if (split && in->strings.n_chars == 0) {
-        // regex_split.cpp:129-143 quirk: an all-empty batch leaves RegexSplit with ragged shape {1} = [0],[0];
         // BPETokenizer then emits one empty row (bpe_tokenizer.cpp:129-131,146-161).
-        const int32_t zero = 0;
-        if (mem == OVTK_MEM_HOST) {
-            out->begins[0] = 0;
-            out->ends[0] = 0;
-        } else {
-            OVTK_HIP(hipMemcpyAsync(out->begins, &zero, 4, hipMemcpyHostToDevice, s));
-            OVTK_HIP(hipMemcpyAsync(out->ends, &zero, 4, hipMemcpyHostToDevice, s));
-            OVTK_HIP(hipStreamSynchronize(s));
-        }
         out->n_rows = 1;
-        return OVTK_OK;
+        return empty_batch_row(out->begins, out->ends, mem, s);
     }
     if (in->n_rows == 0) return OVTK_OK;
 
@@ -845,27 +983,13 @@ int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ov
         RowsIn d_in{};
         if (int rc = stage_input(sw, in, skips, in_mem, s, d_in)) return rc;
         // special_tokens_split.cpp:88-92, + skipped empty strings -- behind one entry per row (special_sparse_kernel's layout)
-        const int64_t cap_extra = in->strings.n_chars + in->strings.n;
-        const int64_t cap = in->n_rows + cap_extra;
-        if (cap >= INT32_MAX) return set_error(OVTK_E_ARG, "tensor sizes must fit int32 offsets");
-        int e = 0;
-        e = e ? e : sw.gen[0].ensure(size_t(d_in.n_rows) * 4);
-        e = e ? e : sw.gen[1].ensure(size_t(d_in.n_rows) * 4);
-        e = e ? e : sw.gen[2].ensure(size_t(cap) * 4);
-        e = e ? e : sw.gen[3].ensure(size_t(cap) * 4);
-        e = e ? e : sw.gen[4].ensure(size_t(cap));
-        if (e) return e;
-        // one pass, a wave per 64 rows, every wave's strings in a region of their own (special_sparse_kernel)
-        if (int rc = sw.status.ensure(sizeof(RunStatus))) return rc;
-        OVTK_HIP(hipMemsetAsync(sw.status.as<void>(), 0, sizeof(RunStatus), s));
-        OVTK_LAUNCH(sw.marks, "special_split", special_sparse_kernel, (d_in.n_rows + kWave - 1) / kWave, kBlockThreads, s, d_in,
-                    special->dev, sw.status.as<RunStatus>(), (long long)cap_extra, sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(),
-                    sw.gen[2].as<int32_t>(), sw.gen[3].as<int32_t>(), sw.gen[4].as<uint8_t>());
-        OVTK_HIP(hipMemcpyAsync(sw.host_status, sw.status.as<RunStatus>(), sizeof(RunStatus), hipMemcpyDeviceToHost, s));   // (read at finish)
-        special_out = ovtk_ragged_strings{sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(), in->n_rows,
-                                          ovtk_strings{sw.gen[2].as<int32_t>(), sw.gen[3].as<int32_t>(), d_in.chars, cap, in->strings.n_chars}};
+        if (in->n_rows + in->strings.n_chars + in->strings.n >= INT32_MAX) return set_error(OVTK_E_ARG, "tensor sizes must fit int32 offsets");
+        SparseStage t;
+        if (int rc = special_sparse_stage(special, sw, d_in, s, t)) return rc;
+        OVTK_HIP(hipMemcpyAsync(sw.host_status, t.st, sizeof(RunStatus), hipMemcpyDeviceToHost, s));   // (read at finish)
+        special_out = ovtk_ragged_strings{t.rb, t.re, in->n_rows, ovtk_strings{t.b, t.e, d_in.chars, t.cap, in->strings.n_chars}};
         in = &special_out;
-        skips = sw.gen[4].as<uint8_t>();
+        skips = t.sk;
     }
     const int in_mem2 = special ? OVTK_MEM_DEVICE : in_mem;
     // A split the lookup kernel has no scanner for (the compiled DFA, the class patterns, max_splits): the pieces are
@@ -885,41 +1009,19 @@ int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ov
         if (int rc = stage_input(sw, in, skips, in_mem2, s, d_in)) return rc;
         const int64_t cap = in->strings.n_chars + in->strings.n;  // regex_split.cpp:182
         if (cap >= INT32_MAX) return set_error(OVTK_E_ARG, "tensor sizes must fit int32 offsets");
-        int e = 0;
-        e = e ? e : sw.gen[0].ensure(size_t(d_in.n_rows) * 4);
-        e = e ? e : sw.gen[1].ensure(size_t(d_in.n_rows) * 4);
-        e = e ? e : sw.gen[2].ensure(size_t(cap) * 4);
-        e = e ? e : sw.gen[3].ensure(size_t(cap) * 4);
-        if (e) return e;
-        int64_t n_pieces = 0;
+        SparseStage t;
+        int64_t n_pieces = cap;   // (the one-pass form: the offsets index the whole buffers)
         if (split->dev.kind == kSplitGeneral) {
             // the compiled DFA in one pass: every row's pieces in a region of its own inside the buffers of the reference's
             // capacity, the ragged begins / ends pointing there -- nothing is counted, the host does not wait (regex_device.hpp)
-            if (int rc = sw.status.ensure(sizeof(RunStatus))) return rc;
-            OVTK_HIP(hipMemsetAsync(sw.status.as<void>(), 0, sizeof(RunStatus), s));
-            const int lane_grid = (d_in.n_rows + kBlockThreads - 1) / kBlockThreads;
-            const RegexSparseLds lay = regex_sparse_layout(split->regex.n_states * split->regex.n_syms, split->regex.cp_blocks_bytes);
-            note_launch(sw.marks, s);
-            Profiler& pf = Profiler::get();
-            if (pf.enabled()) pf.begin("regex_split", s, sw.marks);
-            if (split->mode == 1 && split->max_splits == -1)
-                hipLaunchKernelGGL(regex_sparse_kernel<true>, dim3(lane_grid), dim3(kBlockThreads), size_t(lay.total), s, d_in, split->regex,
-                                   sw.status.as<RunStatus>(), (long long)cap, sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(),
-                                   sw.gen[2].as<int32_t>(), sw.gen[3].as<int32_t>(), (uint8_t*)nullptr);
-            else
-                hipLaunchKernelGGL(regex_sparse_kernel<false>, dim3(lane_grid), dim3(kBlockThreads), size_t(lay.total), s, d_in, split->regex,
-                                   sw.status.as<RunStatus>(), (long long)cap, sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(),
-                                   sw.gen[2].as<int32_t>(), sw.gen[3].as<int32_t>(), (uint8_t*)nullptr);
-            if (pf.enabled()) pf.end(s, sw.marks);
-            OVTK_HIP(hipMemcpyAsync(sw.host_status, sw.status.as<RunStatus>(), sizeof(RunStatus), hipMemcpyDeviceToHost, s));   // (read at finish)
+            if (int rc = regex_sparse_stage(split, sw, d_in, s, /*skips=*/false, t)) return rc;
+            OVTK_HIP(hipMemcpyAsync(sw.host_status, t.st, sizeof(RunStatus), hipMemcpyDeviceToHost, s));   // (read at finish)
             sparse_status = true;
-            n_pieces = cap;   // (the offsets index the whole buffers)
-        } else if (int rc = split_on_device(split, sw, d_in, s, sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(), sw.gen[2].as<int32_t>(),
-                                            sw.gen[3].as<int32_t>(), nullptr, cap, &n_pieces))
-            return rc;
-        pieces = ovtk_ragged_strings{sw.gen[0].as<int32_t>(), sw.gen[1].as<int32_t>(), in->n_rows,
-                                     ovtk_strings{sw.gen[2].as<int32_t>(), sw.gen[3].as<int32_t>(), d_in.chars, n_pieces,
-                                                  in->strings.n_chars}};
+        } else {   // (a hand-written scanner's count and write passes, with their own status block: they count, the host waits)
+            if (int rc = sparse_buffers(sw, d_in.n_rows, cap, /*skips=*/false, /*status=*/false, s, t)) return rc;
+            if (int rc = split_on_device(split, sw, d_in, s, t.rb, t.re, t.b, t.e, nullptr, cap, &n_pieces)) return rc;
+        }
+        pieces = ovtk_ragged_strings{t.rb, t.re, in->n_rows, ovtk_strings{t.b, t.e, d_in.chars, n_pieces, in->strings.n_chars}};
         in = &pieces;
         skips = nullptr;  // BPETokenizer has no skips input: skipped strings arrive as whole pieces
         split = nullptr;
@@ -931,194 +1033,32 @@ int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ov
         bpe->store_pause.fetch_sub(1, std::memory_order_relaxed);
         T.store = PieceStoreDev{nullptr, 30, nullptr, 0};
     }
+    const EncodePlan plan = plan_encode(split, bpe, T);
+    const BpeKernels k{plan, split ? split->dev : SplitDev{}, T, dev, s};
     auto r = make_rows_run(dev, "BPETokenizer", in, skips, 1 + T.suffix_len, out, mem, s,
-                           [=](Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) {
-                               const bool tickets = w.rows_per_ticket != 0;
-                               const bool llama3 = split && split->dev.kind == kSplitLlama3;
-                               const int family = split ? split->dev.family : int(kFamNone);
-                               if (w.small) {  // the whole call in one launch of one block
-                                   const SplitDev sd = split ? split->dev : SplitDev{};
-                                   const bool nar = bpe->narrow_ids;
-#define OVTK_SMALL(MODE)                                                                                                          \
-    do {                                                                                                                          \
-        if (nar) OVTK_LAUNCH(ws.marks, "encode_small", (encode_small_kernel<MODE, true>), grid, kBlockThreads, s, d_in, sd, T, w); \
-        else OVTK_LAUNCH(ws.marks, "encode_small", (encode_small_kernel<MODE, false>), grid, kBlockThreads, s, d_in, sd, T, w);    \
-    } while (0)
-                                   if (llama3) OVTK_SMALL(kFusedLlama3);
-                                   else if (family) OVTK_SMALL(kFusedSeq);
-                                   else if (split) OVTK_SMALL(kFused);
-                                   else OVTK_SMALL(kPieces);
-#undef OVTK_SMALL
-                                   return;
-                               }
-                               if (llama3 && tickets)
-                                   OVTK_LAUNCH(ws.marks, "lookup_fused", (lookup_kernel<kFusedLlama3, true>), grid, kBlockThreads, s, d_in,
-                                               split->dev, T, w);
-                               else if (llama3) {
-                                   // several rows per scan block, the rule algebra on bit masks (lookup_span_kernel<kSpanLlama3>, span_l3.hpp;
-                                   // round 4's row-per-scan kernel stays for handles without a memo); what it leaves goes through the
-                                   // generic kernel
-                                   EncodeWork w1 = w;
-                                   const int grid1 = rows_grid(d_in.n_rows, grid, w1.rows_per_wave);
-                                   if (!(w.launch_mask & kLaunchSpan)) {}   // (the short path's second set of launches: the span kernel has run)
-                                   else if (T.pieces.slots && w1.stage16)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanLlama3, true>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (T.pieces.slots)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanLlama3, false>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else
-                                       OVTK_LAUNCH(ws.marks, "lookup_rows", lookup_rows_kernel<kRowsLlama3>, grid1, kBlockThreads, s, d_in, split->dev,
-                                                   T, w1);
-                                   EncodeWork w2 = w;
-                                   w2.only_pending = 1;
-                                   if (w.launch_mask & kLaunchPending)
-                                       OVTK_LAUNCH(ws.marks, "lookup_fused", lookup_kernel<kFusedLlama3>, grid, kBlockThreads, s, d_in, split->dev,
-                                                   T, w2);
-                               }
-                               else if (family && tickets)
-                                   OVTK_LAUNCH(ws.marks, "lookup_fused", (lookup_kernel<kFusedSeq, true>), grid, kBlockThreads, s, d_in,
-                                               split->dev, T, w);
-                               else if (family) {
-                                   // DeepSeek-V3's pattern, o200k_base: the scan of span_fam.hpp on the span kernel's blocks; the rows it leaves
-                                   // (several strings, skipped ones) are matched literally, a lane per row's window
-                                   EncodeWork w1 = w;
-                                   const int grid1 = rows_grid(d_in.n_rows, grid, w1.rows_per_wave);
-                                   if (!(w.launch_mask & kLaunchSpan)) {}
-                                   else if (family == kFamDs3 && w1.stage16)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanDs3, true>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (family == kFamDs3)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanDs3, false>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (w1.stage16)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanO200k, true>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanO200k, false>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   EncodeWork w2 = w;
-                                   w2.only_pending = 1;
-                                   if (w.launch_mask & kLaunchPending)
-                                       OVTK_LAUNCH(ws.marks, "lookup_fused", lookup_kernel<kFusedSeq>, grid, kBlockThreads, s, d_in, split->dev, T, w2);
-                               }
-                               else if (split && tickets)
-                                   OVTK_LAUNCH(ws.marks, "lookup_fused", (lookup_kernel<kFused, true>), grid, kBlockThreads, s, d_in,
-                                               split->dev, T, w);
-                               else if (split && split->dev.kind <= kSplitGpt2Digits) {
-                                   // several rows per scan block: lookup_span_kernel (it probes the memo for every piece: a handle
-                                   // without one -- cache_capacity = 0 -- takes the row-per-scan kernel); whatever they leave
-                                   // (marked in row_used, listed in pending_rows) goes through the generic kernel
-                                   EncodeWork w1 = w;
-                                   const int grid1 = rows_grid(d_in.n_rows, grid, w1.rows_per_wave);
-                                   if (!(w.launch_mask & kLaunchSpan)) {}
-                                   else if (T.pieces.slots && split->dev.kind == kSplitGpt2Digits && w1.stage16)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanGpt2Digits, true>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (T.pieces.slots && split->dev.kind == kSplitGpt2Digits)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanGpt2Digits, false>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (T.pieces.slots && w1.stage16)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanGpt2, true>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (T.pieces.slots)
-                                       OVTK_LAUNCH(ws.marks, "lookup_span", (lookup_span_kernel<kSpanGpt2, false>), grid1, kBlockThreads, s, d_in, split->dev, T, w1);
-                                   else if (split->dev.kind == kSplitGpt2Digits)
-                                       OVTK_LAUNCH(ws.marks, "lookup_rows", lookup_rows_kernel<kRowsGpt2Digits>, grid1, kBlockThreads, s, d_in,
-                                                   split->dev, T, w1);
-                                   else
-                                       OVTK_LAUNCH(ws.marks, "lookup_rows", lookup_rows_kernel<kRowsGpt2>, grid1, kBlockThreads, s, d_in, split->dev,
-                                                   T, w1);
-                                   // what it left: the generic kernel (it returns at once when nothing was left).  A smaller stand-by
-                                   // grid for handles whose last call left no row was measured: nothing gained on all-ASCII text
-                                   // (6.0 vs 6.2 us), and the rows that do turn up then wait for 64 blocks to walk every row's flag
-                                   EncodeWork w2 = w;
-                                   w2.only_pending = 1;
-                                   if (w.launch_mask & kLaunchPending)
-                                       OVTK_LAUNCH(ws.marks, "lookup_fused", lookup_kernel<kFused>, grid, kBlockThreads, s, d_in, split->dev,
-                                                   T, w2);
-                               } else if (split)
-                                   OVTK_LAUNCH(ws.marks, "lookup_fused", lookup_kernel<kFused>, grid, kBlockThreads, s, d_in,
-                                               split->dev, T, w);
-                               else if (tickets)
-                                   OVTK_LAUNCH(ws.marks, "lookup_pieces", (lookup_kernel<kPieces, true>), grid, kBlockThreads, s, d_in,
-                                               SplitDev{}, T, w);
-                               else
-                                   OVTK_LAUNCH(ws.marks, "lookup_pieces", lookup_kernel<kPieces>, grid, kBlockThreads, s, d_in,
-                                               SplitDev{}, T, w);
-                               if (!(w.launch_mask & kLaunchMerge)) return;   // (the short path: nothing is expected to be left to merge)
-                               const int tail_rows = w.fold_tail ? d_in.n_rows : 0;
-                               if (bpe->narrow_ids) {
-                                   static const int per_cu = resident_blocks_per_cu(merge_kernel<true>);
-                                   OVTK_LAUNCH(ws.marks, "bpe_merge", merge_kernel<true>,
-                                               dim3(kShards, grid_deferred_hinted(grid_deferred_per_shard(d_in.n_chars, d_in.n_strings, device_cu_count(dev) * per_cu / kShards), w.span_sums, w.merge_hint)),
-                                               kBlockThreads, s, d_in, T, w, tail_rows, w.out_cap);
-                               } else {
-                                   static const int per_cu = resident_blocks_per_cu(merge_kernel<false>);
-                                   OVTK_LAUNCH(ws.marks, "bpe_merge", merge_kernel<false>,
-                                               dim3(kShards, grid_deferred_hinted(grid_deferred_per_shard(d_in.n_chars, d_in.n_strings, device_cu_count(dev) * per_cu / kShards), w.span_sums, w.merge_hint)),
-                                               kBlockThreads, s, d_in, T, w, tail_rows, w.out_cap);
-                               }
-                               if (!w.fold_tail) OVTK_LAUNCH(ws.marks, "bpe_exact", exact_kernel, 64, kBlockThreads, s, d_in, T, w);
+                           [k](Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) {
+                               if (w.small) k.small(ws, d_in, w, grid);
+                               else launch_middle(k.plan, k, ws, d_in, w, grid);
                            },
-                           /*self_alloc=*/true,
-                           !split ? resident_blocks_per_cu(lookup_kernel<kPieces>)
-                                  : split->dev.family != kFamNone
-                                      ? (!row_tickets().load(std::memory_order_relaxed) ? resident_blocks_per_cu(lookup_span_kernel<kSpanO200k, false>)
-                                                                                        : resident_blocks_per_cu(lookup_kernel<kFusedSeq>))
-                                  : split->dev.kind == kSplitLlama3
-                                      ? (T.pieces.slots && !row_tickets().load(std::memory_order_relaxed)
-                                             ? resident_blocks_per_cu(lookup_span_kernel<kSpanLlama3, false>)
-                                             : resident_blocks_per_cu(lookup_kernel<kFusedLlama3>))
-                                  : split->dev.kind <= kSplitGpt2Digits && !row_tickets().load(std::memory_order_relaxed)
-                                      ? resident_blocks_per_cu(lookup_span_kernel<kSpanGpt2, true>, 6)
-                                      : resident_blocks_per_cu(lookup_kernel<kFused>),
-                           /*tail_in_middle=*/true);
+                           &plan);
     if (pieces_ws) r->also_settles(pieces_ws);
     if (special_ws) r->also_settles(special_ws);
     if (special_ws || sparse_status) {
         std::shared_ptr<WorkspaceLease> sparse_ws = sparse_status ? pieces_ws : nullptr;
-        r->front_check([special_ws, sparse_ws]() -> int {
-            if (special_ws) {
-                const RunStatus& st = *special_ws->ws->host_status;
-                if (st.flags & kFlagRange) return set_error(OVTK_E_RANGE, "input begins/ends index outside their tensors");
-                if (st.flags & kFlagOutCapacity) return set_error(OVTK_E_CAPACITY, "SpecialTokensSplit: more strings than the reference's capacity");
-            }
-            if (sparse_ws && (sparse_ws->ws->host_status->flags & kFlagOutCapacity))
-                return set_error(OVTK_E_CAPACITY, "RegexSplit: the strings overlap -- their pieces need more room than the reference's n_chars + n_strings "
-                                                  "(regex_split.cpp:182)");
-            return OVTK_OK;
-        });
+        r->front_check([special_ws, sparse_ws]() { return check_front_stages(special_ws.get(), sparse_ws.get()); });
     }
     if (pieces_ws || special_ws)
         r->input_on_device(std::make_shared<std::tuple<std::shared_ptr<void>, std::shared_ptr<void>, std::shared_ptr<void>>>(pieces_ws, special_ws, device_inputs));
     else if (device_inputs)
         r->input_on_device(device_inputs);
     const bool has_store = T.store.slots != nullptr;
-    // The short path (span_kernel.hpp): where the call's first kernel is lookup_span_kernel, the kernels behind it are launched only when
-    // the handle's last calls had work for them.
-    const bool short_path = split && (split->dev.kind <= kSplitGpt2Digits || split->dev.kind == kSplitLlama3 || split->dev.family != kFamNone) && T.pieces.slots &&
-                            !row_tickets().load(std::memory_order_relaxed) && short_path_mode().load(std::memory_order_relaxed) != 0;
-    if (short_path)
-        r->enable_short_path(bpe->expect_pending.load(std::memory_order_relaxed) > 0, bpe->expect_merge.load(std::memory_order_relaxed) > 0 || !has_store,
-                             has_store ? bpe->last_unresolved.load(std::memory_order_relaxed) : -1);
-    if (has_store || dense_width || short_path)   // what the store did for this call decides whether the next ones ask it at all
+    if (plan.short_ok) r->expect(bpe->predict.arm(has_store));
+    if (has_store || dense_width || plan.short_ok)
         r->on_status([bpe, has_store, dense_width](const RunStatus& st) {
             if (dense_width) *dense_width = st.width;
-            if (st.short_path) {   // the span kernel counted: what this call's text left to the kernels of the middle
-                auto note = [](std::atomic<int>& expect, bool had_work) {
-                    if (had_work) expect.store(kShortPathKeep, std::memory_order_relaxed);
-                    else if (expect.load(std::memory_order_relaxed) > 0) expect.fetch_sub(1, std::memory_order_relaxed);
-                };
-                note(bpe->expect_pending, st.n_pending > 0);
-                if (st.short_path != 3) {   // (3: the long way, nothing was counted)
-                    note(bpe->expect_merge, st.n_unresolved > 0);
-                    bpe->last_unresolved.store(st.n_unresolved, std::memory_order_relaxed);
-                }
-            }
-            if (!has_store) return;
-            if (st.n_store_probe < 256) return;   // (counted by one wave in 64)
-            // (a cold store misses everything too: only a run of such calls says that the text is the reason)
-            if (st.n_store_hit * 8 >= st.n_store_probe) bpe->store_low.store(0, std::memory_order_relaxed);
-            else if (bpe->store_low.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
-                bpe->store_low.store(0, std::memory_order_relaxed);
-                bpe->store_pause.store(32, std::memory_order_relaxed);
-            }
+            bpe->predict.note(st);
+            if (has_store) note_store_use(bpe, st);
         });
-    if (!row_tickets().load(std::memory_order_relaxed)) r->enable_small();
-    if (bpe->stage16) r->enable_stage16();
-    if (split && (split->dev.kind <= kSplitGpt2Digits || split->dev.kind == kSplitLlama3 || split->dev.family != kFamNone) && T.pieces.slots) r->stage_twice();   // (lookup_span_kernel in front of the generic kernel)
     if (wire) r->output_to_wire(*wire);
     if (dense) r->output_dense(*dense);
     if (int rc = r->start()) return rc;
@@ -1127,14 +1067,33 @@ int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ov
 }
 
 int run_encode(const ovtk_regex_split* split, const ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
-               ovtk_ragged_i32_out* out, int mem, void* stream) {
+               ovtk_ragged_i32_out* out, int mem, void* stream, const ovtk_special_tokens_split* special) {
     std::unique_ptr<PendingRun> run;
-    if (int rc = start_encode(split, bpe, in, skips, out, mem, stream, run)) return rc;
+    if (int rc = start_encode(split, bpe, in, skips, out, mem, stream, run, nullptr, nullptr, special)) return rc;
     return run ? run->finish(out) : OVTK_OK;
 }
 
-int check_fused(const ovtk_regex_split* split) {
-    if (!split) return set_error(OVTK_E_ARG, "null split handle");
+// The split ops' device-side outputs: the caller's pointers, or workspace buffers that copy_split_outputs() copies back.
+int split_targets(Workspace& ws, const ovtk_ragged_strings_out* out, int n_rows, int mem, int32_t** d_rb, int32_t** d_re, int32_t** d_b, int32_t** d_e,
+                  uint8_t** d_sk) {
+    int e = 0;
+    e = e ? e : out_target(ws.out_a, out->ragged_begins, size_t(n_rows) * 4, mem, d_rb);
+    e = e ? e : out_target(ws.out_b, out->ragged_ends, size_t(n_rows) * 4, mem, d_re);
+    e = e ? e : out_target(ws.out_c, out->begins, size_t(out->capacity) * 4, mem, d_b);
+    e = e ? e : out_target(ws.out_d, out->ends, size_t(out->capacity) * 4, mem, d_e);
+    if (out->skips) e = e ? e : out_target(ws.out_e, out->skips, size_t(out->capacity), mem, d_sk);
+    return e;
+}
+// The split ops' outputs back to a host caller: the rows' begins / ends and the first n_out strings.
+int copy_split_outputs(ovtk_ragged_strings_out* out, int64_t n_rows, int64_t n_out, const int32_t* d_rb, const int32_t* d_re, const int32_t* d_b,
+                       const int32_t* d_e, const uint8_t* d_sk, int mem, hipStream_t s) {
+    if (mem != OVTK_MEM_HOST) return OVTK_OK;
+    OVTK_HIP(hipMemcpyAsync(out->ragged_begins, d_rb, size_t(n_rows) * 4, hipMemcpyDeviceToHost, s));
+    OVTK_HIP(hipMemcpyAsync(out->ragged_ends, d_re, size_t(n_rows) * 4, hipMemcpyDeviceToHost, s));
+    OVTK_HIP(hipMemcpyAsync(out->begins, d_b, size_t(n_out) * 4, hipMemcpyDeviceToHost, s));
+    OVTK_HIP(hipMemcpyAsync(out->ends, d_e, size_t(n_out) * 4, hipMemcpyDeviceToHost, s));
+    if (out->skips) OVTK_HIP(hipMemcpyAsync(out->skips, d_sk, size_t(n_out), hipMemcpyDeviceToHost, s));
+    OVTK_HIP(hipStreamSynchronize(s));
     return OVTK_OK;
 }
 
@@ -1148,36 +1107,32 @@ int ovtk_bpe_run(ovtk_bpe* h, const ovtk_ragged_strings* in, ovtk_ragged_i32_out
 
 int ovtk_encode_run(ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
                     ovtk_ragged_i32_out* out, int mem, void* stream) {
-    if (int rc = check_fused(split)) return rc;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
     return run_encode(split, bpe, in, skips, out, mem, stream);
 }
 
 int ovtk_encode_special_run(ovtk_special_tokens_split* special, ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in,
                             const uint8_t* skips, ovtk_ragged_i32_out* out, int mem, void* stream) {
     if (!special) return set_error(OVTK_E_ARG, "null special-tokens handle");
-    if (int rc = check_fused(split)) return rc;
-    std::unique_ptr<PendingRun> run;
-    if (int rc = start_encode(split, bpe, in, skips, out, mem, stream, run, nullptr, nullptr, special)) return rc;
-    return run ? run->finish(out) : OVTK_OK;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
+    return run_encode(split, bpe, in, skips, out, mem, stream, special);
 }
 
 int ovtk_encode_special_enqueue(ovtk_special_tokens_split* special, ovtk_regex_split* split, ovtk_bpe* bpe,
                                 const ovtk_ragged_strings* in, const uint8_t* skips, const ovtk_ragged_i32_out* out, void* stream,
                                 ovtk_pending** pending) {
     if (!pending || !out || !special) return set_error(OVTK_E_ARG, "null argument");
-    if (int rc = check_fused(split)) return rc;
-    auto p = std::make_unique<ovtk_pending>();
-    p->out = *out;
-    if (int rc = start_encode(split, bpe, in, skips, &p->out, OVTK_MEM_DEVICE, stream, p->run, nullptr, nullptr, special)) return rc;
-    *pending = p.release();
-    return OVTK_OK;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
+    return enqueue_pending(*out, pending, [&](ovtk_pending& p) {
+        return start_encode(split, bpe, in, skips, &p.out, OVTK_MEM_DEVICE, stream, p.run, nullptr, nullptr, special);
+    });
 }
 
 int ovtk_encode_dense_enqueue(ovtk_special_tokens_split* special, ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in,
                               const uint8_t* skips, const ovtk_dense_params* params, int32_t* out_ids, uint8_t* out_mask, int64_t capacity,
                               void* stream, ovtk_pending** pending) {
     if (!pending || !params || !out_ids || !in || capacity < 0) return set_error(OVTK_E_ARG, "null argument");
-    if (int rc = check_fused(split)) return rc;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
     if (params->n_prefix < 0 || params->n_prefix > kDenseAffix || params->n_suffix < 0 || params->n_suffix > kDenseAffix ||
         (params->n_prefix && !params->prefix) || (params->n_suffix && !params->suffix) || params->max_length < 0)
         return set_error(OVTK_E_ARG, "encode_dense: at most 4 constant ids in front / behind, max_length >= 0");
@@ -1261,29 +1216,21 @@ int ovtk_set_row_tickets(int rows_per_ticket) {
 int ovtk_encode_enqueue(ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
                         const ovtk_ragged_i32_out* out, void* stream, ovtk_pending** pending) {
     if (!pending || !out) return set_error(OVTK_E_ARG, "null argument");
-    if (int rc = check_fused(split)) return rc;
-    auto p = std::make_unique<ovtk_pending>();
-    p->out = *out;
-    if (int rc = start_encode(split, bpe, in, skips, &p->out, OVTK_MEM_DEVICE, stream, p->run)) return rc;
-    *pending = p.release();
-    return OVTK_OK;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
+    return enqueue_pending(*out, pending, [&](ovtk_pending& p) { return start_encode(split, bpe, in, skips, &p.out, OVTK_MEM_DEVICE, stream, p.run); });
 }
 
 int ovtk_encode_enqueue_host(ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
                              const ovtk_ragged_i32_out* out, void* stream, ovtk_pending** pending) {
     if (!pending || !out) return set_error(OVTK_E_ARG, "null argument");
-    if (int rc = check_fused(split)) return rc;
-    auto p = std::make_unique<ovtk_pending>();
-    p->out = *out;
-    if (int rc = start_encode(split, bpe, in, skips, &p->out, OVTK_MEM_HOST, stream, p->run)) return rc;
-    *pending = p.release();
-    return OVTK_OK;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
+    return enqueue_pending(*out, pending, [&](ovtk_pending& p) { return start_encode(split, bpe, in, skips, &p.out, OVTK_MEM_HOST, stream, p.run); });
 }
 
 int ovtk_encode_enqueue_wire(ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips, void* wire,
                              int64_t max_rows, int64_t pad_ids, int id_bytes, void* stream, ovtk_pending** pending) {
     if (!pending || !wire || !in) return set_error(OVTK_E_ARG, "null argument");
-    if (int rc = check_fused(split)) return rc;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
     if ((id_bytes != 2 && id_bytes != 4) || pad_ids < 0 || pad_ids % 8 || pad_ids >= INT32_MAX || max_rows % 4 || in->n_rows > max_rows)
         return set_error(OVTK_E_ARG, "encode to wire: bad wire geometry (ovtk_shard_max_rows / pad_ids / id_bytes of the exchange)");
     if (int rc = check_rows(in)) return rc;
@@ -1315,7 +1262,7 @@ int ovtk_encode_enqueue_wire(ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_
 int ovtk_encode_enqueue_packed(ovtk_regex_split* split, ovtk_bpe* bpe, const uint8_t* packed, int64_t n_bytes,
                                const ovtk_ragged_i32_out* out, int out_mem, void* stream, ovtk_pending** pending) {
     if (!pending || !out || !packed || !bpe) return set_error(OVTK_E_ARG, "null argument");
-    if (int rc = check_fused(split)) return rc;
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
     if (out_mem != OVTK_MEM_HOST && out_mem != OVTK_MEM_DEVICE) return set_error(OVTK_E_ARG, "out_mem must be OVTK_MEM_HOST or OVTK_MEM_DEVICE");
     // the reference's format checks (src/utils.cpp:21-25), on the host copy
     if (n_bytes < 4) return set_error(OVTK_E_ARG, "Incorrect packed string tensor format: no batch size in the packed string tensor");
@@ -1381,19 +1328,10 @@ int ovtk_regex_split_run(ovtk_regex_split* h, const ovtk_ragged_strings* in, con
     OVTK_HIP(hipSetDevice(h->device));
     out->n = 0;
     out->n_rows = in->n_rows;
-    if (in->strings.n_chars == 0) {  // regex_split.cpp:129-143
-        const int32_t zero = 0;
-        if (mem == OVTK_MEM_HOST) {
-            out->ragged_begins[0] = 0;
-            out->ragged_ends[0] = 0;
-        } else {
-            OVTK_HIP(hipMemcpyAsync(out->ragged_begins, &zero, 4, hipMemcpyHostToDevice, s));
-            OVTK_HIP(hipMemcpyAsync(out->ragged_ends, &zero, 4, hipMemcpyHostToDevice, s));
-            OVTK_HIP(hipStreamSynchronize(s));
-        }
+    if (in->strings.n_chars == 0) {
         out->n_rows = 1;
         out->n = -1;
-        return OVTK_OK;
+        return empty_batch_row(out->ragged_begins, out->ragged_ends, mem, s);
     }
     if (in->n_rows == 0) return OVTK_OK;
     WorkspaceLease ws(h->device);
@@ -1403,13 +1341,7 @@ int ovtk_regex_split_run(ovtk_regex_split* h, const ovtk_ragged_strings* in, con
     const int n_rows = d_in.n_rows;
     int32_t *d_rb = nullptr, *d_re = nullptr, *d_b = nullptr, *d_e = nullptr;
     uint8_t* d_sk = nullptr;
-    int e = 0;
-    e = e ? e : out_target(ws->out_a, out->ragged_begins, size_t(n_rows) * 4, mem, &d_rb);
-    e = e ? e : out_target(ws->out_b, out->ragged_ends, size_t(n_rows) * 4, mem, &d_re);
-    e = e ? e : out_target(ws->out_c, out->begins, size_t(out->capacity) * 4, mem, &d_b);
-    e = e ? e : out_target(ws->out_d, out->ends, size_t(out->capacity) * 4, mem, &d_e);
-    if (out->skips) e = e ? e : out_target(ws->out_e, out->skips, size_t(out->capacity), mem, &d_sk);
-    if (e) return e;
+    if (int rc = split_targets(*ws.ws, out, n_rows, mem, &d_rb, &d_re, &d_b, &d_e, &d_sk)) return rc;
     int64_t n_out = 0;
     bool done = false;
     if ((long long)d_in.n_chars + d_in.n_strings < INT32_MAX) {   // one pass over the text (a compiled pattern: the automaton runs once)
@@ -1431,15 +1363,7 @@ int ovtk_regex_split_run(ovtk_regex_split* h, const ovtk_ragged_strings* in, con
     if (!done)
         if (int rc = split_on_device(h, *ws.ws, d_in, s, d_rb, d_re, d_b, d_e, d_sk, out->capacity, &n_out)) return rc;
     out->n = n_out;
-    if (mem == OVTK_MEM_HOST) {
-        OVTK_HIP(hipMemcpyAsync(out->ragged_begins, d_rb, size_t(n_rows) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->ragged_ends, d_re, size_t(n_rows) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->begins, d_b, size_t(n_out) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->ends, d_e, size_t(n_out) * 4, hipMemcpyDeviceToHost, s));
-        if (out->skips) OVTK_HIP(hipMemcpyAsync(out->skips, d_sk, size_t(n_out), hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipStreamSynchronize(s));
-    }
-    return OVTK_OK;
+    return copy_split_outputs(out, n_rows, n_out, d_rb, d_re, d_b, d_e, d_sk, mem, s);
 }
 
 int ovtk_special_tokens_split_run(ovtk_special_tokens_split* h, const ovtk_ragged_strings* in, const uint8_t* skips,
@@ -1456,15 +1380,9 @@ int ovtk_special_tokens_split_run(ovtk_special_tokens_split* h, const ovtk_ragge
     RowsIn d_in{};
     if (int rc = stage_input(*ws.ws, in, skips, mem, s, d_in)) return rc;
     const int n_rows = d_in.n_rows;
-    int e = 0;
     int32_t *d_rb = nullptr, *d_re = nullptr, *d_b = nullptr, *d_e = nullptr;
     uint8_t* d_sk = nullptr;
-    e = e ? e : out_target(ws->out_a, out->ragged_begins, size_t(n_rows) * 4, mem, &d_rb);
-    e = e ? e : out_target(ws->out_b, out->ragged_ends, size_t(n_rows) * 4, mem, &d_re);
-    e = e ? e : out_target(ws->out_c, out->begins, size_t(out->capacity) * 4, mem, &d_b);
-    e = e ? e : out_target(ws->out_d, out->ends, size_t(out->capacity) * 4, mem, &d_e);
-    e = e ? e : out_target(ws->out_e, out->skips, size_t(out->capacity), mem, &d_sk);
-    if (e) return e;
+    if (int rc = split_targets(*ws.ws, out, n_rows, mem, &d_rb, &d_re, &d_b, &d_e, &d_sk)) return rc;   // (out->skips: checked above)
     bool one_pass = (long long)d_in.n_rows + d_in.n_chars + d_in.n_strings < INT32_MAX;   // (the one-pass form's buffers: the three-pass form has none)
     if (one_pass) {
         if (int rc = special_one_pass(h, *ws.ws, d_in, s, d_rb, d_re, d_b, d_e, d_sk, (long long)out->capacity)) return rc;
@@ -1481,15 +1399,7 @@ int ovtk_special_tokens_split_run(ovtk_special_tokens_split* h, const ovtk_ragge
     if (st.flags & kFlagRange) return set_error(OVTK_E_RANGE, "input begins/ends index outside their tensors");
     if (st.flags & kFlagOutCapacity) return set_error(OVTK_E_CAPACITY, "SpecialTokensSplit: output begins/ends too small");
     out->n = st.n_out;
-    if (mem == OVTK_MEM_HOST) {
-        OVTK_HIP(hipMemcpyAsync(out->ragged_begins, d_rb, size_t(n_rows) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->ragged_ends, d_re, size_t(n_rows) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->begins, d_b, size_t(st.n_out) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->ends, d_e, size_t(st.n_out) * 4, hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipMemcpyAsync(out->skips, d_sk, size_t(st.n_out), hipMemcpyDeviceToHost, s));
-        OVTK_HIP(hipStreamSynchronize(s));
-    }
-    return OVTK_OK;
+    return copy_split_outputs(out, n_rows, st.n_out, d_rb, d_re, d_b, d_e, d_sk, mem, s);
 }
 
 }  // extern "C"

@@ -99,7 +99,7 @@ struct ovtk_wordpiece {
     int32_t store_capacity = 0;
     PieceTableDev memo{nullptr, 30, nullptr, 0, 0};  // word -> ids of every vocabulary word (the fused path's first-level lookup)
     int64_t n_vocab = 0;   // ids are vocabulary indices: below 65535 (and unk_token_id too), a call stages u16 entries
-    std::atomic<int> expect_pending{0}, expect_merge{kShortPathKeep}, last_unresolved{-1};   // the short path's predictors (api_encode.cpp ovtk_bpe says how they count)
+    ShortPathPredictor predict;   // the short path: lookup_kernel<kFused> / wordpiece_deferred_kernel only when the last calls had rows / words for them
 };
 
 struct ovtk_vocab_encoder {
@@ -194,6 +194,38 @@ int ovtk_wordpiece_run(ovtk_wordpiece* h, const ovtk_ragged_strings* in, int32_t
 
 }  // extern "C"
 namespace {
+// The kernels of the fused WordPiece encode for launch_middle() (api_common.hpp).
+struct WordpieceKernels {
+    EncodePlan plan;
+    SplitDev sp;
+    BpeDev memo_only;
+    WordpieceDev wdev;
+    int32_t unk_token_id;
+    int device;
+    hipStream_t s;
+
+    // rows that are one ASCII window: lookup_rows_kernel (consecutive rows per wave, the next row's text requested ahead:
+    // encode_kernels.hpp); several rows per scan block (span_kernel.hpp) where there is a word memo to probe
+    void front(Workspace& ws, const RowsIn& d_in, const EncodeWork& w1, int grid1) const {
+        if (plan.front == kFrontSpan)
+            with_bool(w1.stage16 != 0, [&](auto s16) {
+                OVTK_LAUNCH(ws.marks, plan.front_tag, (lookup_span_kernel<kSpanBertWords, decltype(s16)::value>), grid1, kBlockThreads, s, d_in, sp, memo_only, w1);
+            });
+        else
+            OVTK_LAUNCH(ws.marks, plan.front_tag, lookup_rows_kernel<kRowsBertWords>, grid1, kBlockThreads, s, d_in, sp, memo_only, w1);
+    }
+    void lookup(Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid, const char* tag) const {
+        OVTK_LAUNCH(ws.marks, tag, lookup_kernel<kFused>, grid, kBlockThreads, s, d_in, sp, memo_only, w);
+    }
+    void deferred(Workspace& ws, const RowsIn& d_in, const EncodeWork& w) const {
+        const dim3 dgrid(grid_deferred_hinted(grid_deferred_per_shard(d_in.n_chars, d_in.n_strings, device_cu_count(device) * 8 / kShards), w.span_sums, w.merge_hint), kShards);
+        with_bool(w.stage16 != 0, [&](auto s16) {
+            OVTK_LAUNCH(ws.marks, "wordpiece_deferred", wordpiece_deferred_kernel<decltype(s16)::value>, dgrid, kBlockThreads, s, d_in, wdev, unk_token_id, w,
+                        w.fold_tail ? d_in.n_rows : 0, w.out_cap);
+        });
+    }
+};
+
 // Launches the fused BERT split + WordPiece kernels; `run` stays empty when the result was complete without any.
 int start_wordpiece_encode(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk_regex_split* delimiters,
                            const ovtk_ragged_strings* in, int32_t unk_token_id, ovtk_ragged_i32_out* out, int mem,
@@ -211,18 +243,9 @@ int start_wordpiece_encode(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk
     OVTK_HIP(hipSetDevice(h->device));
     out->n_data = 0;
     out->n_rows = in->n_rows;
-    if (in->strings.n_chars == 0) {  // regex_split.cpp:129-143: the first split leaves one empty row
-        const int32_t zero = 0;
-        if (mem == OVTK_MEM_HOST) {
-            out->begins[0] = 0;
-            out->ends[0] = 0;
-        } else {
-            OVTK_HIP(hipMemcpyAsync(out->begins, &zero, 4, hipMemcpyHostToDevice, s));
-            OVTK_HIP(hipMemcpyAsync(out->ends, &zero, 4, hipMemcpyHostToDevice, s));
-            OVTK_HIP(hipStreamSynchronize(s));
-        }
+    if (in->strings.n_chars == 0) {  // the first split leaves one empty row
         out->n_rows = 1;
-        return OVTK_OK;
+        return empty_batch_row(out->begins, out->ends, mem, s);
     }
     if (in->n_rows == 0) return OVTK_OK;
     SplitDev sp = whitespace->dev;
@@ -233,65 +256,22 @@ int start_wordpiece_encode(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk
     memo_only.store = h->dev.store;   // (the short path: lookup_span_kernel looks the words the memo does not hold up in the word store itself)
     memo_only.suffix_len = 0;
     memo_only.unk_id = unk_token_id;   // (what a word-store entry without a segmentation comes back as)
-    const int dev = h->device;
-    const WordpieceDev wdev = h->dev;
-    auto r = make_rows_run(dev, "WordpieceTokenizer", in, nullptr, 1, out, mem, s,
-                           [=](Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) {
-                               // rows that are one ASCII window: lookup_rows_kernel (consecutive rows per wave, the next row's text
-                                   // requested ahead: encode_kernels.hpp); what it leaves -- marked in row_used -- goes through the
-                                   // generic kernel
-                               EncodeWork w1 = w;
-                               const int grid1 = rows_grid(d_in.n_rows, grid, w1.rows_per_wave);
-                               if (!w.rows_per_ticket) {
-                                   // several rows per scan block (span_kernel.hpp) where there is a word memo to probe
-                                   if (!(w.launch_mask & kLaunchSpan)) {}   // (the short path's second set of launches: the span kernel has run)
-                                   else if (memo_only.pieces.slots && w1.stage16)
-                                       OVTK_LAUNCH(ws.marks, "lookup_words", (lookup_span_kernel<kSpanBertWords, true>), grid1, kBlockThreads, s, d_in, sp,
-                                                   memo_only, w1);
-                                   else if (memo_only.pieces.slots)
-                                       OVTK_LAUNCH(ws.marks, "lookup_words", (lookup_span_kernel<kSpanBertWords, false>), grid1, kBlockThreads, s, d_in, sp,
-                                                   memo_only, w1);
-                                   else
-                                       OVTK_LAUNCH(ws.marks, "lookup_words", lookup_rows_kernel<kRowsBertWords>, grid1, kBlockThreads, s, d_in, sp,
-                                                   memo_only, w1);
-                                   EncodeWork w2 = w;
-                                   w2.only_pending = 1;
-                                   if (w.launch_mask & kLaunchPending)
-                                       OVTK_LAUNCH(ws.marks, "lookup_fused", lookup_kernel<kFused>, grid, kBlockThreads, s, d_in, sp, memo_only, w2);
-                               } else {
-                                   OVTK_LAUNCH(ws.marks, "lookup_words", lookup_kernel<kFused>, grid, kBlockThreads, s, d_in, sp, memo_only, w);
-                               }
-                               if (!(w.launch_mask & kLaunchMerge)) return;   // (the short path: no word is expected to be left for the tries)
-                               const dim3 dgrid(grid_deferred_hinted(grid_deferred_per_shard(d_in.n_chars, d_in.n_strings, device_cu_count(dev) * 8 / kShards), w.span_sums, w.merge_hint), kShards);
-                               if (w.stage16)
-                                   OVTK_LAUNCH(ws.marks, "wordpiece_deferred", wordpiece_deferred_kernel<true>, dgrid, kBlockThreads, s, d_in, wdev,
-                                               unk_token_id, w, w.fold_tail ? d_in.n_rows : 0, w.out_cap);
-                               else
-                                   OVTK_LAUNCH(ws.marks, "wordpiece_deferred", wordpiece_deferred_kernel<false>, dgrid, kBlockThreads, s, d_in, wdev,
-                                               unk_token_id, w, w.fold_tail ? d_in.n_rows : 0, w.out_cap);
-                           },
-                           /*self_alloc=*/true,
-                           memo_only.pieces.slots ? resident_blocks_per_cu(lookup_span_kernel<kSpanBertWords, true>) : resident_blocks_per_cu(lookup_kernel<kFused>),
-                           /*tail_in_middle=*/true);
-    if (h->n_vocab > 0 && h->n_vocab <= 65535 && unk_token_id >= 0 && unk_token_id <= 65534) r->enable_stage16();
-    if (memo_only.pieces.slots) r->stage_twice();   // (lookup_span_kernel in front of the generic kernel)
-    // The short path (span_kernel.hpp): lookup_kernel<kFused> / wordpiece_deferred_kernel only when the handle's last calls had rows /
-    // words for them (as a BPE handle does: api_encode.cpp).
-    if (memo_only.pieces.slots && !row_tickets().load(std::memory_order_relaxed) && short_path_mode().load(std::memory_order_relaxed) != 0) {
-        r->enable_short_path(h->expect_pending.load(std::memory_order_relaxed) > 0, h->expect_merge.load(std::memory_order_relaxed) > 0 || !memo_only.store.slots,
-                             memo_only.store.slots ? h->last_unresolved.load(std::memory_order_relaxed) : -1);
-        r->on_status([h](const RunStatus& st) {
-            if (!st.short_path) return;
-            auto note = [](std::atomic<int>& expect, bool had_work) {
-                if (had_work) expect.store(kShortPathKeep, std::memory_order_relaxed);
-                else if (expect.load(std::memory_order_relaxed) > 0) expect.fetch_sub(1, std::memory_order_relaxed);
-            };
-            note(h->expect_pending, st.n_pending > 0);
-            if (st.short_path != 3) {   // (3: the long way, nothing was counted)
-                note(h->expect_merge, st.n_unresolved > 0);
-                h->last_unresolved.store(st.n_unresolved, std::memory_order_relaxed);
-            }
-        });
+    const bool has_memo = memo_only.pieces.slots != nullptr;
+    EncodePlan plan;
+    plan.mode = kFused;
+    plan.front_tag = plan.whole_tag = "lookup_words";
+    plan.rest_tag = "lookup_fused";
+    plan.stage16 = h->n_vocab > 0 && h->n_vocab <= 65535 && unk_token_id >= 0 && unk_token_id <= 65534;
+    // (under row tickets the plain lookup_kernel<kFused> takes every row, rows_per_ticket set; no one-launch form)
+    plan_front(plan, kSpanBertWords, has_memo, /*ticketed_form=*/false, /*small_form=*/false);
+    plan.blocks_per_cu = has_memo ? resident_blocks_per_cu(lookup_span_kernel<kSpanBertWords, true>) : resident_blocks_per_cu(lookup_kernel<kFused>);
+    const WordpieceKernels k{plan, sp, memo_only, h->dev, unk_token_id, h->device, s};
+    auto r = make_rows_run(h->device, "WordpieceTokenizer", in, nullptr, 1, out, mem, s,
+                           [k](Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) { launch_middle(k.plan, k, ws, d_in, w, grid); },
+                           &plan);
+    if (plan.short_ok) {
+        r->expect(h->predict.arm(memo_only.store.slots != nullptr));
+        r->on_status([h](const RunStatus& st) { h->predict.note(st); });
     }
     if (int rc = r->start()) return rc;
     run = std::move(r);
@@ -312,11 +292,9 @@ int ovtk_wordpiece_encode_enqueue(ovtk_wordpiece* h, ovtk_regex_split* whitespac
                                   const ovtk_ragged_strings* in, int32_t unk_token_id, const ovtk_ragged_i32_out* out,
                                   void* stream, ovtk_pending** pending) {
     if (!pending || !out) return set_error(OVTK_E_ARG, "null argument");
-    auto p = std::make_unique<ovtk_pending>();
-    p->out = *out;
-    if (int rc = start_wordpiece_encode(h, whitespace, delimiters, in, unk_token_id, &p->out, OVTK_MEM_DEVICE, stream, p->run)) return rc;
-    *pending = p.release();
-    return OVTK_OK;
+    return enqueue_pending(*out, pending, [&](ovtk_pending& p) {
+        return start_wordpiece_encode(h, whitespace, delimiters, in, unk_token_id, &p.out, OVTK_MEM_DEVICE, stream, p.run);
+    });
 }
 
 void ovtk_wordpiece_destroy(ovtk_wordpiece* h) { delete h; }
