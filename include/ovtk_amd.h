@@ -475,6 +475,39 @@ int ovtk_unigram_create(const ovtk_strings* vocab, const float* scores, const ov
 int ovtk_unigram_run(ovtk_unigram* h, const ovtk_ragged_strings* in, ovtk_ragged_i32_out* out, int mem, void* stream);
 void ovtk_unigram_destroy(ovtk_unigram* h);
 
+/* ---------------------------------------------------------------- CharsMapNormalization / NormalizeUnicode / CaseFold
+ * ovtk_charsmap_run replaces CharsMapNormalization::evaluate (src/charsmap_normalization.cpp:34-69), NormalizeUnicode::evaluate
+ * (src/normalize_unicode.cpp:32-62) and CaseFold::evaluate with encoding "utf-8" (src/case_fold.cpp:34-73): all three run
+ * sentencepiece's normalizer::Normalizer::Normalize over a precompiled charsmap, per string, inside evaluate_normalization_helper
+ * (src/utils.cpp:178-234), and differ in the blob and the three flags alone.  `blob`: u32 trie_size | trie_size bytes of Darts
+ * double-array units | NUL-terminated replacement strings, host memory, consumed at create (the reference's lazy init, :37-58);
+ * blob_len 0: no trie.  Bit-exact, quirks included: of the first 32 keys that match at a position the longest wins; a byte that
+ * starts no well-formed character is U+FFFD for ONE byte; with remove_extra_whitespaces and escape_whitespaces the strip at the
+ * end eats a literal U+2581 of the input too; an empty string stays empty (no dummy prefix).  treat_whitespace_as_suffix is always
+ * false in the reference's ops and does not exist here.
+ * A malformed blob is OVTK_E_UNSUPPORTED (never an out-of-bounds read on the device): the size field past the end, trie_size not a
+ * multiple of 4, a key's value outside the replacement strings or a replacement without its NUL, a unit array whose walk does not end.
+ * Limits (OVTK_E_UNSUPPORTED): a replacement longer than 1 023 bytes; with both whitespace flags, a replacement that ends in the
+ * first one or two bytes of U+2581.
+ * out: begins/ends [in->n], written back to back from 0 whatever the input offsets were (:226-232).  skips (or NULL): u8 [in->n],
+ * a row with skips[i] != 0 is copied unchanged (:211); the caller passes skips through.  The reference sizes chars after the fact;
+ * here ovtk_charsmap_bound(h, n, n_chars) is an upper bound for any input of n strings and n_chars bytes (the handle's largest
+ * replacement / key ratio, x3 under escape_whitespaces, at least 3 for U+FFFD, + 3 per row for the dummy prefix), and a smaller
+ * buffer is fine when the text fits: OVTK_E_CAPACITY otherwise, out->n_chars = the bytes the call needs, nothing written.
+ * ovtk_case_fold_ascii replaces CaseFold::evaluate with encoding "" (:56-64, case_fold.hpp:21-23): bytes 'A'..'Z' + 32 (lower != 0)
+ * or 'a'..'z' - 32, same layout of the outputs; out->chars capacity: the bytes of the strings. */
+typedef struct ovtk_charsmap ovtk_charsmap;
+typedef struct ovtk_charsmap_params {
+    int add_dummy_prefix;
+    int remove_extra_whitespaces;
+    int escape_whitespaces;
+} ovtk_charsmap_params;
+int ovtk_charsmap_create(const uint8_t* blob, int64_t blob_len, const ovtk_charsmap_params* params, int device, ovtk_charsmap** out);
+int ovtk_charsmap_run(ovtk_charsmap* h, const ovtk_strings* in, const uint8_t* skips, ovtk_strings_out* out, int mem, void* stream);
+int64_t ovtk_charsmap_bound(ovtk_charsmap* h, int64_t n, int64_t n_chars);
+void ovtk_charsmap_destroy(ovtk_charsmap* h);
+int ovtk_case_fold_ascii(const ovtk_strings* in, int lower, ovtk_strings_out* out, int mem, int device, void* stream);
+
 /* ---------------------------------------------------------------- UTF8Validate
  * Replaces UTF8Validate::evaluate, src/utf8_validate.cpp:18-143.  replace_mode 0: drop invalid bytes, 1: U+FFFD.
  * out->begins/ends: [in->n]; out->chars capacity: the reference allocates 3 * in->n_chars (:31-33).  Offsets start

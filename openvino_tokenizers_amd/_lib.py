@@ -73,6 +73,10 @@ class UnigramParams(C.Structure):
     _fields_ = [("unk_token_id", C.c_int32), ("byte_fallback", C.c_int), ("fuse_unk", C.c_int)]
 
 
+class CharsmapParams(C.Structure):
+    _fields_ = [("add_dummy_prefix", C.c_int), ("remove_extra_whitespaces", C.c_int), ("escape_whitespaces", C.c_int)]
+
+
 class StringsOut(C.Structure):
     _fields_ = [("begins", C.c_void_p), ("ends", C.c_void_p), ("chars", C.c_void_p), ("chars_capacity", C.c_int64),
                 ("n_chars", C.c_int64)]
@@ -111,6 +115,7 @@ EXPORTS = [
     "ovtk_utf8_validate", "ovtk_truncate", "ovtk_combine_segments", "ovtk_encode_tail_run",
     "ovtk_trie_tokenizer_create", "ovtk_trie_tokenizer_run", "ovtk_trie_tokenizer_destroy",
     "ovtk_unigram_create", "ovtk_unigram_run", "ovtk_unigram_destroy",
+    "ovtk_charsmap_create", "ovtk_charsmap_run", "ovtk_charsmap_bound", "ovtk_charsmap_destroy", "ovtk_case_fold_ascii",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -152,6 +157,13 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_shard_wire_bytes.restype = C.c_int64
     lib.ovtk_string_tensor_packed_bytes.restype = C.c_int64
     lib.ovtk_shard_max_rows.restype = C.c_int64
+    lib.ovtk_charsmap_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(CharsmapParams), C.c_int, C.POINTER(C.c_void_p)]
+    lib.ovtk_charsmap_run.argtypes = [C.c_void_p, C.POINTER(Strings), C.c_void_p, C.POINTER(StringsOut), C.c_int, C.c_void_p]
+    lib.ovtk_charsmap_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+    lib.ovtk_charsmap_bound.restype = C.c_int64
+    lib.ovtk_charsmap_destroy.argtypes = [C.c_void_p]
+    lib.ovtk_charsmap_destroy.restype = None
+    lib.ovtk_case_fold_ascii.argtypes = [C.POINTER(Strings), C.c_int, C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
     _cache[key] = lib
     return lib
 

@@ -867,6 +867,148 @@ class UTF8Validate(_Op):
         return [ob[:len(b)], oe[:len(b)], oc[:out.n_chars]]
 
 
+class CharsMapNormalization(_Op):
+    """Reference: src/charsmap_normalization.cpp (validate :13-31, evaluate :34-69).  Strings (3) [+ skips (bool)] [+ charsmap u8]
+    -> strings (3) [+ skips].  3, 4 or 5 inputs: input 3 is skips when it is boolean (or when a fifth input follows), and the
+    precompiled charsmap is the LAST input when normalization_form == "".  Attributes as the reference's.  A named form needs its
+    table: this library ships none (the reference generates precompiled_charsmap.hpp at build time), so the blob comes in as
+    `charsmap=` bytes -- charsmaps.from_sentencepiece(rule_name) returns one where the sentencepiece package is installed."""
+
+    def __init__(self, add_dummy_prefix=False, remove_extra_whitespaces=True, escape_whitespaces=False, normalization_form="",
+                 case_fold=False, nmt=False, charsmap=None, device=0, lib=None):
+        super().__init__(device, lib)
+        self.add_dummy_prefix, self.remove_extra_whitespaces = bool(add_dummy_prefix), bool(remove_extra_whitespaces)
+        self.escape_whitespaces, self.normalization_form = bool(escape_whitespaces), str(normalization_form)
+        self.case_fold, self.nmt = bool(case_fold), bool(nmt)
+        self._blob = None if charsmap is None else _bytes_of(charsmap)
+        if self.normalization_form != "" and self._blob is None:
+            raise L.OvtkError(L.E_ARG, f"CharsMapNormalization: normalization_form `{self.normalization_form}` needs its precompiled charsmap and "
+                                       "this library ships none: pass charsmap=<bytes> (charsmaps.from_sentencepiece(rule_name) gives sentencepiece's)")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ovtk_charsmap_destroy(self._h)
+            self._h = None
+
+    def _split_inputs(self, inputs):
+        """-> (skips or None, blob or None) of the inputs behind the three string tensors."""
+        n = len(inputs)
+        if n not in (3, 4, 5):
+            raise L.OvtkError(L.E_ARG, "CharsMapNormalization supports input sizes 3, 4 or 5.")   # charsmap_normalization.cpp:15
+        if n == 5:
+            return inputs[3], inputs[4]
+        if n == 4:
+            x = inputs[3]
+            is_bool = str(getattr(x, "dtype", "")) in ("bool", "torch.bool")
+            if is_bool or self.normalization_form != "":   # :21, :35
+                return x, None
+            return None, x
+        return None, None
+
+    def _ensure(self, blob):
+        if self._h:
+            return
+        if self.normalization_form == "":
+            if blob is None and self._blob is None:
+                raise L.OvtkError(L.E_ARG, "CharsMapNormalization: normalization_form is \"\" and no charsmap input was given")
+            data = _bytes_of(blob) if blob is not None else self._blob
+        else:
+            data = self._blob
+        buf = np.frombuffer(data, np.uint8)
+        p = L.CharsmapParams(int(self.add_dummy_prefix), int(self.remove_extra_whitespaces), int(self.escape_whitespaces))
+        self._chk(self._lib.ovtk_charsmap_create(buf.ctypes.data_as(C.c_void_p) if len(buf) else None, C.c_int64(len(buf)), C.byref(p),
+                                                 self.device, C.byref(self._h)))
+
+    def bound(self, n, n_chars):
+        """Bytes the output of n strings of n_chars bytes can take (ovtk_charsmap_bound); the handle must exist (after a first evaluate)."""
+        return int(self._lib.ovtk_charsmap_bound(self._h, C.c_int64(n), C.c_int64(n_chars)))
+
+    def evaluate(self, inputs, chars_capacity=None):
+        skips, blob = self._split_inputs(inputs)
+        self._ensure(blob)
+        m = _Mem(inputs[2])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        c, pc = m.inp(inputs[2], "u8")
+        psk = None
+        if skips is not None:
+            _, psk = m.inp(skips, "bool")
+        ob, pob = m.alloc(len(b), "i32")
+        oe, poe = m.alloc(len(b), "i32")
+        s = L.Strings(pb, pe, pc, len(b), len(c))
+        # most text grows little: a first buffer of that size, and the size the library reports where it did not do
+        cap = min(self.bound(len(b), len(c)), len(c) + len(c) // 4 + 3 * len(b) + 64) if chars_capacity is None else int(chars_capacity)
+        for attempt in range(2):
+            oc, poc = m.alloc(cap, "u8")
+            out = L.StringsOut(pob, poe, poc, cap, 0)
+            rc = self._lib.ovtk_charsmap_run(self._h, C.byref(s), psk, C.byref(out), m.mem, m.stream)
+            if rc != L.E_CAPACITY or chars_capacity is not None or attempt:
+                break
+            cap = int(out.n_chars)
+        self._chk(rc)
+        res = [ob[:len(b)], oe[:len(b)], oc[:out.n_chars]]
+        return res + [skips] if skips is not None else res
+
+
+class NormalizeUnicode(CharsMapNormalization):
+    """Reference: src/normalize_unicode.cpp (evaluate :32-62): the charsmap of `normalization_form` (NFC, NFD, NFKC, NFKD) with all three
+    flags off.  Strings (3) [+ skips] -> strings (3) [+ skips].  `charsmap=`: the form's precompiled table (see CharsMapNormalization)."""
+
+    def __init__(self, normalization_form="NFD", charsmap=None, device=0, lib=None):
+        if charsmap is None:
+            raise L.OvtkError(L.E_ARG, f"NormalizeUnicode: the precompiled charsmap of `{normalization_form}` is needed and this library ships none: "
+                                       "pass charsmap=<bytes>")
+        super().__init__(False, False, False, normalization_form=str(normalization_form), charsmap=charsmap, device=device, lib=lib)
+
+    def _split_inputs(self, inputs):
+        if len(inputs) not in (3, 4):
+            raise L.OvtkError(L.E_ARG, "NormalizeUnicode supports input sizes 3 or 4.")
+        return (inputs[3] if len(inputs) == 4 else None), None
+
+
+class CaseFold(_Op):
+    """Reference: src/case_fold.cpp (validate :11-32, evaluate :34-73).  Strings (3) [+ skips] -> strings (3) [+ skips].
+    encoding "": the byte range 'A'..'Z' + 32 (lower) or 'a'..'z' - 32 -- every row: the reference does not hand its skips to the
+    helper on this branch (:57-64).  encoding "utf-8" (lower only): sentencepiece's case-folding identity charsmap with all flags off,
+    rows with skips copied; `charsmap=`: that table (see CharsMapNormalization)."""
+
+    def __init__(self, encoding="utf-8", lower=True, charsmap=None, device=0, lib=None):
+        super().__init__(device, lib)
+        self.encoding, self.lower = str(encoding), bool(lower)
+        if self.encoding not in ("", "utf-8") or (self.encoding == "utf-8" and not self.lower):   # case_fold.cpp:13-19
+            raise L.OvtkError(L.E_ARG, "CaseFold operation `encoding` attribute must be either \"\" or \"utf-8\". When `encoding` is \"utf-8\", "
+                                       f"only `lower` = true is supported. Got encoding = `{self.encoding}` and lower = {self.lower}.")
+        self._map = None
+        if self.encoding == "utf-8":
+            if charsmap is None:
+                raise L.OvtkError(L.E_ARG, "CaseFold: encoding \"utf-8\" needs the case-folding charsmap and this library ships none: pass charsmap=<bytes>")
+            self._map = CharsMapNormalization(False, False, False, normalization_form="identity", case_fold=True, charsmap=charsmap, device=device, lib=lib)
+
+    def evaluate(self, inputs):
+        if len(inputs) not in (3, 4):
+            raise L.OvtkError(L.E_ARG, "supported input sizes are 3 or 4")   # case_fold.cpp:24
+        if self._map is not None:
+            return self._map.evaluate(inputs)
+        m = _Mem(inputs[2])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        c, pc = m.inp(inputs[2], "u8")
+        ob, pob = m.alloc(len(b), "i32")
+        oe, poe = m.alloc(len(b), "i32")
+        s = L.Strings(pb, pe, pc, len(b), len(c))
+        cap = len(c)   # (more only where strings overlap in the chars tensor: the library reports the size)
+        for attempt in range(2):
+            oc, poc = m.alloc(cap, "u8")
+            out = L.StringsOut(pob, poe, poc, cap, 0)
+            rc = self._lib.ovtk_case_fold_ascii(C.byref(s), int(self.lower), C.byref(out), m.mem, self.device, m.stream)
+            if rc != L.E_CAPACITY or attempt:
+                break
+            cap = int(out.n_chars)
+        self._chk(rc)
+        res = [ob[:len(b)], oe[:len(b)], oc[:out.n_chars]]
+        return res + [inputs[3]] if len(inputs) == 4 else res
+
+
 class FuzeRagged(_Op):
     """Reference: src/fuze.cpp (evaluate :20-40).  ragged_begins, ragged_ends, begins, ends -> begins, ends."""
 

@@ -16,7 +16,8 @@ through the C ABI, one library call per node -- what `core.add_extension()` + th
   Truncate CombineSegments Padding                              -> FusedEncodeTailStep        ovtk_encode_tail_run
   VocabDecoder [ByteFallback] FuzeRagged                        -> FusedDetokenizeStep        ovtk_detokenize_run
 
-and leaves every other step as it is.  The rewritten list gives the same outputs as the original one (tests/test_pipeline_fuse.py:
+and leaves every other step as it is -- the normalizers (CharsmapStep, NormalizeUnicode, CaseFoldStep) among them: a chain behind them
+is fused as if they were not there.  The rewritten list gives the same outputs as the original one (tests/test_pipeline_fuse.py:
 bit for bit, on BASELINE.json's configurations); adapter/fuse_pass.cpp is the same recogniser over ov::Node chains.
 """
 from __future__ import annotations
@@ -53,6 +54,52 @@ class Step:
 
     def apply(self, kind, vals):
         raise NotImplementedError
+
+
+class _NormalizationStep(Step):
+    """A normalizer in front of the splits: strings -> strings, the ragged rows and the skips passed through."""
+
+    def apply(self, kind, vals):
+        assert kind == "strings"
+        rb, re_, b, e, c = vals[:5]
+        skips = vals[5] if len(vals) > 5 else None
+        out = self.op.evaluate([b, e, c] + ([skips] if skips is not None else []))
+        return "strings", [rb, re_] + list(out[:3]) + [skips]
+
+
+class CharsmapStep(_NormalizationStep):
+    """src/charsmap_normalization.cpp:34-69 (tokenizer_pipeline.py:293-352): sentencepiece's normalizer over a precompiled charsmap --
+    `charsmap` bytes, the table of `normalization_form` where that is given (this library ships none)."""
+
+    def __init__(self, charsmap=None, normalization_form=None, add_dummy_prefix=False, remove_extra_whitespaces=True, escape_whitespaces=False,
+                 case_fold=False, nmt=False, lib=None):
+        if charsmap is None:
+            raise ValueError("CharsmapStep: a precompiled charsmap is needed (charsmap=<bytes>); this library ships no tables")
+        self.charsmap = bytes(charsmap)
+        self.op = K.CharsMapNormalization(add_dummy_prefix, remove_extra_whitespaces, escape_whitespaces, normalization_form=normalization_form or "",
+                                          case_fold=case_fold, nmt=nmt, charsmap=self.charsmap, lib=lib)
+
+
+class NormalizeUnicode(_NormalizationStep):
+    """src/normalize_unicode.cpp:32-62 (tokenizer_pipeline.py:168-190): the charsmap of NFD / NFC / NFKD / NFKC, every flag off."""
+
+    def __init__(self, normalization_form="NFD", charsmap=None, lib=None):
+        if normalization_form not in ("NFD", "NFC", "NFKD", "NFKC"):
+            raise ValueError(f'[ NormalizeUnicode ] `normalization_form` attribute must be one of ["NFD", "NFC", "NFKD", "NFKC"], got {normalization_form}.')
+        if charsmap is None:
+            raise ValueError("NormalizeUnicode: the form's precompiled charsmap is needed (charsmap=<bytes>); this library ships no tables")
+        self.normalization_form = normalization_form
+        self.op = K.NormalizeUnicode(normalization_form.lower(), charsmap=charsmap, lib=lib)
+
+
+class CaseFoldStep(_NormalizationStep):
+    """src/case_fold.cpp:34-73 (tokenizer_pipeline.py:194-220): encoding "" shifts the ASCII range, "utf-8" runs the case-folding charsmap."""
+
+    def __init__(self, encoding="utf-8", charsmap=None, lib=None):
+        if encoding not in ("", "utf-8"):
+            raise ValueError(f"[ CaseFoldStep ] `encoding` attribute must be one of ['', 'utf-8'], got {encoding!r}.")
+        self.encoding = encoding
+        self.op = K.CaseFold(encoding=encoding, lower=True, charsmap=charsmap, lib=lib)
 
 
 class SpecialTokensSplitStep(Step):

@@ -3,7 +3,7 @@ on a config-2-shaped batch (65 536 rows x ~512 bytes of zipf text, a GPT-2 speci
 batch for the ops behind the tokenizer), inputs and outputs in HBM:
 
     UTF8Validate (both modes), SpecialTokensSplit (the op: count pass, scan, write pass), RegexSplit (the op), StringTensorPack /
-    StringTensorUnpack, TrieTokenizer, UnigramTokenizer, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
+    StringTensorUnpack, TrieTokenizer, UnigramTokenizer, CharsMapNormalization, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
     (ovtk_encode_tail_run: Truncate -> CombineSegments -> RaggedToDense x 2 in one call).
 
 Per op one JSON line: wall time per call (Python + the library's host side + the kernels; the call returns when its results are
@@ -175,6 +175,24 @@ def main():
           f"V = {len(uni_vocab)} (256 bytes + the batch's {len(words)} words and their prefixes), {n_words} strings, {steps} trie steps: a lane per byte "
           "walks the trie, a lane per string relaxes and back-tracks")
     del ws_out
+    # ---- CharsMapNormalization (src/charsmap_normalization.cpp:34-69): sentencepiece's nmt_nfkc_cf table (tests/golden/golden_charsmap.npz) with
+    # XLM-RoBERTa's flags, on the batch as it is and with 5 % of its characters replaced by capitals, which the table rewrites; the check
+    # is tests/charsmap_ref.py on the first rows
+    from openvino_tokenizers_amd.ops import CharsMapNormalization
+    from tests.charsmap_ref import CharsMapRef
+    cm_blob = bytes(np.load(Path(__file__).resolve().parent.parent / "tests" / "golden" / "golden_charsmap.npz")["blob_nmt_nfkc_cf"])
+    cm_flags = dict(add_dummy_prefix=True, remove_extra_whitespaces=True, escape_whitespaces=True)
+    cm_ref = CharsMapRef(cm_blob, **cm_flags)
+    c_rw = c.copy()
+    c_rw[np.random.default_rng(3).random(n_c) < 0.05] = ord("Q")
+    for label, text in (("as is", c), ("5 % rewritten", c_rw)):
+        cm = CharsMapNormalization(lib=lib, **cm_flags)
+        d_text = text if args.emu else torch.as_tensor(text, device=dev)
+        ref_cm = cm_ref(b[:k], e[:k], text)
+        cm_out = timed(f"CharsMapNormalization(nmt_nfkc_cf, {label})", lambda cm=cm, d_text=d_text: cm.evaluate([d[2], d[3], d_text, np.frombuffer(cm_blob, np.uint8)]),
+                       n_c + 16 * n + int(n_c * 1.03), lambda out, ref_cm=ref_cm: same(ref_cm[:2], [to_np(out[0])[:k], to_np(out[1])[:k]]) and same([ref_cm[2]], [to_np(out[2])], upto=len(ref_cm[2])),
+                       "a wave per row counts, a scan, a wave per row writes: the trie is walked twice")
+        del cm_out
     # ---- the ids of the batch (the fused encode), then the ops behind the tokenizer
     fused = FusedSplitBPE(RegexSplit("isolate", lib=lib), BPETokenizer(**tok.attrs, lib=lib))
     ib, ie, ids = fused.evaluate(d + [pat], tok.consts)
