@@ -508,6 +508,44 @@ int64_t ovtk_charsmap_bound(ovtk_charsmap* h, int64_t n, int64_t n_chars);
 void ovtk_charsmap_destroy(ovtk_charsmap* h);
 int ovtk_case_fold_ascii(const ovtk_strings* in, int lower, ovtk_strings_out* out, int mem, int device, void* stream);
 
+/* ---------------------------------------------------------------- RegexNormalization
+ * ovtk_regex_normalization_run replaces RegexNormalization::evaluate (src/regex_normalization.cpp:127-153): per string,
+ * PCRE2Wrapper::substitute (src/utils.cpp:315-382) = pcre2_substitute with PCRE2_UTF | PCRE2_UCP, inside
+ * evaluate_normalization_helper (src/utils.cpp:178-234).  PCRE2 is not run on the device: create compiles pattern and template into
+ * matcher tables and a substitution plan (csrc/regex_subst.hpp).  Bit-exact, with the reference's quirks:
+ *  - the three old search patterns of src/regex_normalization.cpp:32-36 are rewritten, and `\1`..`\9` in the template become
+ *    `$1`..`$9` (:19-30); the template is PCRE2's non-extended substitute syntax: literal bytes, `$$`, `$n`, `${n}`, `$name`, `${name}`;
+ *  - the op is the identity when PCRE2 rejects the pattern (utils.cpp:318-320), when the template has a syntax error (a trailing `$`
+ *    ...) or refers to a group number or name the pattern does not have (any negative code gives the input back, :363-377);
+ *  - empty matches as pcre2_substitute treats them: behind an empty match at p first a non-empty match anchored at p, else one
+ *    character is copied (`x*` with `-` on `axxb` is `-a--b-`); `^` and look-behind see the original text;
+ *  - a match that leaves a referenced group unset gives the WHOLE string back (PCRE2 error -55): `(a)|b` with `[$1]` on `ab` is `ab`;
+ *  - the reference's buffer holds 4 * (len + rc * template_len) bytes, rc = pcre2_match's return value for the first match (1 + the
+ *    highest group set), template_len = the reformatted template's; a string whose result + 1 does not fit comes back unchanged.
+ *    Where unreferenced optional groups leave rc open and a result falls between the two sizes, the call is OVTK_E_UNSUPPORTED;
+ *  - global_replace == 0: the first match only.
+ * OVTK_E_UNSUPPORTED at create, never an approximation: pattern syntax outside csrc/regex_compile.hpp's subset (back-references
+ * ...), a template reference to a group whose span is not fixed relative to the match -- under a quantifier, inside an inner
+ * alternation, or with surroundings of variable length (top-level alternatives may differ: each is compiled on its own), or inside a look-around --, `$*MARK`.
+ * out: begins/ends [in->n], written back to back from 0 whatever the input offsets were (:226-232).  skips (or NULL): u8 [in->n], a
+ * row with skips[i] != 0 is copied (:211); the caller passes skips through (:190).  ovtk_regex_normalization_bound(h, n, n_chars) is an
+ * upper bound of the output's bytes; a smaller buffer is fine when the text fits: OVTK_E_CAPACITY otherwise, out->n_chars = the
+ * bytes the call needs, nothing written.  Subjects must be valid UTF-8 (the reference passes PCRE2_NO_UTF_CHECK). */
+typedef struct ovtk_regex_normalization ovtk_regex_normalization;
+typedef struct ovtk_regex_normalization_params {
+    const char* pattern;
+    int64_t pattern_len;
+    const char* replace;
+    int64_t replace_len;
+    int global_replace;
+    int device;
+} ovtk_regex_normalization_params;
+int ovtk_regex_normalization_create(const ovtk_regex_normalization_params* params, ovtk_regex_normalization** out);
+int ovtk_regex_normalization_run(ovtk_regex_normalization* h, const ovtk_strings* in, const uint8_t* skips, ovtk_strings_out* out, int mem,
+                                 void* stream);
+int64_t ovtk_regex_normalization_bound(ovtk_regex_normalization* h, int64_t n, int64_t n_chars);
+void ovtk_regex_normalization_destroy(ovtk_regex_normalization* h);
+
 /* ---------------------------------------------------------------- UTF8Validate
  * Replaces UTF8Validate::evaluate, src/utf8_validate.cpp:18-143.  replace_mode 0: drop invalid bytes, 1: U+FFFD.
  * out->begins/ends: [in->n]; out->chars capacity: the reference allocates 3 * in->n_chars (:31-33).  Offsets start

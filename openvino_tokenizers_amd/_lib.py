@@ -77,6 +77,11 @@ class CharsmapParams(C.Structure):
     _fields_ = [("add_dummy_prefix", C.c_int), ("remove_extra_whitespaces", C.c_int), ("escape_whitespaces", C.c_int)]
 
 
+class RegexNormalizationParams(C.Structure):
+    _fields_ = [("pattern", C.c_char_p), ("pattern_len", C.c_int64), ("replace", C.c_char_p), ("replace_len", C.c_int64),
+                ("global_replace", C.c_int), ("device", C.c_int)]
+
+
 class StringsOut(C.Structure):
     _fields_ = [("begins", C.c_void_p), ("ends", C.c_void_p), ("chars", C.c_void_p), ("chars_capacity", C.c_int64),
                 ("n_chars", C.c_int64)]
@@ -116,6 +121,7 @@ EXPORTS = [
     "ovtk_trie_tokenizer_create", "ovtk_trie_tokenizer_run", "ovtk_trie_tokenizer_destroy",
     "ovtk_unigram_create", "ovtk_unigram_run", "ovtk_unigram_destroy",
     "ovtk_charsmap_create", "ovtk_charsmap_run", "ovtk_charsmap_bound", "ovtk_charsmap_destroy", "ovtk_case_fold_ascii",
+    "ovtk_regex_normalization_create", "ovtk_regex_normalization_run", "ovtk_regex_normalization_bound", "ovtk_regex_normalization_destroy",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -164,6 +170,12 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_charsmap_destroy.argtypes = [C.c_void_p]
     lib.ovtk_charsmap_destroy.restype = None
     lib.ovtk_case_fold_ascii.argtypes = [C.POINTER(Strings), C.c_int, C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_regex_normalization_create.argtypes = [C.POINTER(RegexNormalizationParams), C.POINTER(C.c_void_p)]
+    lib.ovtk_regex_normalization_run.argtypes = [C.c_void_p, C.POINTER(Strings), C.c_void_p, C.POINTER(StringsOut), C.c_int, C.c_void_p]
+    lib.ovtk_regex_normalization_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+    lib.ovtk_regex_normalization_bound.restype = C.c_int64
+    lib.ovtk_regex_normalization_destroy.argtypes = [C.c_void_p]
+    lib.ovtk_regex_normalization_destroy.restype = None
     _cache[key] = lib
     return lib
 

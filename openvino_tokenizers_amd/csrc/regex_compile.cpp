@@ -193,8 +193,14 @@ public:
         if (pos_ != p_.size()) throw Invalid{"unmatched ')'"};
         return root;
     }
+    // the capture groups in the order they were closed: number (as PCRE2 counts opening parentheses, (?| ) branches alike), name, body
+    struct Group { int number; std::string name; int node; };
+    const std::vector<Group>& groups() const { return groups_; }
+    int group_count() const { return group_top_; }
 
 private:
+    std::vector<Group> groups_;
+    int group_next_ = 0, group_top_ = 0;
     std::vector<Node>& nodes_;
     std::vector<uint32_t> p_;
     size_t pos_ = 0;
@@ -249,10 +255,17 @@ private:
         s.normalize();
     }
 
-    int parse_alt(Flags& f) {
+    int parse_alt(Flags& f, bool branch_reset = false) {
         std::vector<int> alts;
+        const int base = group_next_;
+        int top = base;
         alts.push_back(parse_cat(f));
-        while (eat('|')) alts.push_back(parse_cat(f));
+        while (eat('|')) {
+            top = std::max(top, group_next_);
+            if (branch_reset) group_next_ = base;   // (?|...): every branch numbers its groups from the same start
+            alts.push_back(parse_cat(f));
+        }
+        group_next_ = std::max(top, group_next_);
         if (alts.size() == 1) return alts[0];
         Node n;
         n.kind = kAlt;
@@ -698,8 +711,12 @@ private:
 
     int parse_group(Flags& outer) {  // pos_ behind '('
         Flags f = outer;
+        bool capturing = false, branch_reset = false;
+        std::string group_name;
         if (eat('?')) {
-            if (eat(':') || eat('|')) {   // (?|...): the branches number their groups alike -- nothing here looks at group numbers
+            if (eat(':')) {
+            } else if (eat('|')) {   // (?|...): the branches number their groups alike
+                branch_reset = true;
             } else if (peek() == '=' || peek() == '!') {
                 const bool neg = p_[pos_++] == '!';
                 const int body = parse_alt(f);
@@ -746,6 +763,8 @@ private:
                 for (const std::string& seen : group_names_)
                     if (seen == name) throw Invalid{"two named subpatterns have the same name"};
                 group_names_.push_back(name);
+                capturing = true;
+                group_name = name;
             } else {
                 // flag settings: (?i) (?s) (?is) (?-i) ... and the scoped form (?i: ... )
                 bool on = true, any = false;
@@ -784,9 +803,14 @@ private:
             for (const char* k : known)
                 if (name == k) throw Unsupported{"(*VERB)"};
             throw Invalid{"(*VERB) not recognized"};
+        } else {
+            capturing = true;
         }
-        const int body = parse_alt(f);
+        const int number = capturing ? ++group_next_ : 0;
+        group_top_ = std::max(group_top_, group_next_);
+        const int body = parse_alt(f, branch_reset);
         if (!eat(')')) throw Invalid{"missing closing parenthesis"};
+        if (capturing) groups_.push_back(Group{number, group_name, body});
         return body;
     }
 
@@ -997,13 +1021,11 @@ struct Builder {
     }
 };
 
-}  // namespace
+constexpr int kNonEmptyStart = 0x10000;   // in a state's context: a start state of RegexProgram::start_nonempty
 
-int compile_regex(const std::string& pattern, RegexProgram& out, std::string& err) {
-    try {
-        std::vector<Node> nodes;
-        Parser parser(pattern, nodes);
-        const int root = parser.parse();
+// The tables of the pattern whose syntax tree hangs under `root` (throws Unsupported).
+void compile_tree(const std::vector<Node>& nodes, int root, bool want_nonempty, RegexProgram& out) {
+    {
         Builder b{nodes, {}, {}, {}};
         const int match_pc = b.emit(Inst{kMatch});
         const int entry = b.gen(root, match_pc);
@@ -1206,7 +1228,7 @@ int compile_regex(const std::string& pattern, RegexProgram& out, std::string& er
         ids.emplace(states[0], 0);
         auto intern = [&](Key k) {
             if (k.second.empty()) return 0;
-            if (!track_ctx) k.first = 0;
+            if (!track_ctx) k.first &= kNonEmptyStart;
             auto it = ids.find(k);
             if (it != ids.end()) return it->second;
             if (states.size() >= size_t(kRegexMaxStates)) throw Unsupported{"pattern needs more than 4096 DFA states"};
@@ -1216,6 +1238,8 @@ int compile_regex(const std::string& pattern, RegexProgram& out, std::string& er
             return id;
         };
         for (int c = 0; c < n_ctx; ++c) out.start[c] = uint16_t(intern(Key{c, {entry}}));
+        if (want_nonempty)
+            for (int c = 0; c < n_ctx; ++c) out.start_nonempty[c] = uint16_t(intern(Key{c | kNonEmptyStart, {entry}}));
         std::vector<uint16_t> trans;
         std::vector<uint8_t> open(b.prog.size());
         std::set<std::tuple<int, uint64_t, int, int>> visited;
@@ -1317,7 +1341,8 @@ int compile_regex(const std::string& pattern, RegexProgram& out, std::string& er
         for (size_t s = 0; s < states.size(); ++s) {
             trans.resize((s + 1) * size_t(n_syms), 0);
             if (s == 0) continue;
-            const int st_ctx = states[s].first;
+            const int st_ctx = states[s].first & ~kNonEmptyStart;
+            const bool nonempty_start = (states[s].first & kNonEmptyStart) != 0;   // nothing consumed yet, and an empty match does not count
             const std::vector<Item> st_items = unflatten(states[s].second);
             for (int sym = 0; sym < n_syms; ++sym) {
                 const int c = sym_class(sym);
@@ -1410,6 +1435,7 @@ int compile_regex(const std::string& pattern, RegexProgram& out, std::string& er
                             if (!have(pc, e.cid, 0, e.tid)) found.push_back(Found{pc, e.cid, 0, e.tid});
                             break;
                         case kMatch:
+                            if (nonempty_start) break;   // PCRE2 backtracks out of an empty match here: the threads behind it go on
                             if (cl[size_t(e.cid)].empty()) matched = true;   // everything of lower priority is cut
                             else if (!have(-1, e.cid, 0, 0)) found.push_back(Found{-1, e.cid, 0, 0});
                             break;
@@ -1525,23 +1551,161 @@ int compile_regex(const std::string& pattern, RegexProgram& out, std::string& er
             }
             out.cp_index[blk] = uint16_t(it->second);
         }
+    }
+}
+
+// The reference keeps a null pattern (src/utils.cpp:264-271): nothing ever matches.  One dead state, one class.
+void never_matches(RegexProgram& out, const std::string& why) {
+    out = RegexProgram{};
+    out.invalid = true;
+    out.invalid_why = why;
+    out.n_classes = 1;
+    out.sym_eot = 1;
+    out.n_syms = 2;
+    out.n_states = 1;
+    out.trans.assign(2, 0);
+    out.ctx_next.assign(1, 0);
+    out.cp_index.assign((size_t(kMaxCp) + 1) >> 7, 0);
+    out.cp_blocks.assign(128, 0);
+}
+
+// Characters `node` consumes whatever it matches, or -1.
+int fixed_width(const std::vector<Node>& nodes, int node) {
+    const Node& n = nodes[size_t(node)];
+    switch (n.kind) {
+        case kEmpty: case kAssert: case kLookNode: return 0;
+        case kSet: return 1;
+        case kAtomic: return fixed_width(nodes, n.kids[0]);
+        case kRepeat: {
+            const int w = fixed_width(nodes, n.kids[0]);
+            return (n.min == n.max && w >= 0) ? w * n.min : -1;
+        }
+        case kCat: {
+            int sum = 0;
+            for (int k : n.kids) {
+                const int w = fixed_width(nodes, k);
+                if (w < 0) return -1;
+                sum += w;
+            }
+            return sum;
+        }
+        case kAlt: {
+            int w = -1;
+            for (size_t k = 0; k < n.kids.size(); ++k) {
+                const int x = fixed_width(nodes, n.kids[k]);
+                if (x < 0 || (k && x != w)) return -1;
+                w = x;
+            }
+            return w;
+        }
+    }
+    return -1;
+}
+// Is `target` inside `node` (what a look-ahead holds does not count: Parser::atomize shares alternatives with the look-aheads it writes)?
+bool holds_node(const std::vector<Node>& nodes, int node, int target, bool into_look = false) {
+    if (node == target) return true;
+    const Node& n = nodes[size_t(node)];
+    if (n.kind == kLookNode && !into_look) return false;
+    for (int k : n.kids)
+        if (holds_node(nodes, k, target, into_look)) return true;
+    return false;
+}
+// `target` reached from `node` through sequences (and atomic groups) alone: the characters in front of it and behind it, or false.
+bool fixed_place(const std::vector<Node>& nodes, int node, int target, int& front, int& back) {
+    if (node == target) {
+        front = back = 0;
+        return true;
+    }
+    const Node& n = nodes[size_t(node)];
+    if (n.kind == kAtomic) return fixed_place(nodes, n.kids[0], target, front, back);
+    if (n.kind != kCat) return false;
+    for (size_t k = 0; k < n.kids.size(); ++k) {
+        if (!holds_node(nodes, n.kids[k], target)) continue;
+        int f = 0, b = 0;
+        if (!fixed_place(nodes, n.kids[k], target, f, b)) return false;
+        for (size_t j = 0; j < n.kids.size(); ++j) {
+            if (j == k) continue;
+            const int w = fixed_width(nodes, n.kids[j]);
+            if (w < 0) return false;
+            (j < k ? f : b) += w;
+        }
+        front = f;
+        back = b;
+        return true;
+    }
+    return false;
+}
+
+}  // namespace
+
+int compile_regex(const std::string& pattern, RegexProgram& out, std::string& err) {
+    try {
+        std::vector<Node> nodes;
+        Parser parser(pattern, nodes);
+        const int root = parser.parse();
+        compile_tree(nodes, root, false, out);
         return OVTK_OK;
     } catch (const Unsupported& u) {
         err = "RegexSplit: pattern outside the subset compiled for the GPU (" + u.what + "); PCRE2 is not executed on the device";
         return OVTK_E_UNSUPPORTED;
     } catch (const Invalid& v) {
-        // The reference keeps a null pattern (src/utils.cpp:264-271): nothing ever matches.  One dead state, one class.
-        out = RegexProgram{};
+        never_matches(out, v.what);
+        return OVTK_OK;
+    }
+}
+
+int compile_regex_groups(const std::string& pattern, RegexWithGroups& out, std::string& err) {
+    out = RegexWithGroups{};
+    try {
+        std::vector<Node> nodes;
+        Parser parser(pattern, nodes);
+        const int root = parser.parse();
+        compile_tree(nodes, root, true, out.whole);
+        out.n_groups = parser.group_count();
+        for (const Parser::Group& g : parser.groups())
+            if (!g.name.empty()) out.names.emplace_back(g.name, g.number);
+        // the top-level alternatives: the kids of the root when it is an alternation (groups leave no node of their own: a pattern
+        // that is one ( ), (?: ) or (?| ) around an alternation has that alternation as its root)
+        const std::vector<int> tops = nodes[size_t(root)].kind == kAlt ? nodes[size_t(root)].kids : std::vector<int>{root};
+        for (int top : tops) {
+            RegexAlternative a;
+            a.groups.assign(size_t(out.n_groups) + 1, RegexGroupSpan{});
+            a.groups[0] = RegexGroupSpan{0, 0};
+            for (const Parser::Group& g : parser.groups()) {
+                RegexGroupSpan& span = a.groups[size_t(g.number)];
+                int f = 0, b = 0;
+                if (g.node == root) span = RegexGroupSpan{0, 0};   // the group around the whole alternation
+                else if (fixed_place(nodes, top, g.node, f, b)) span = RegexGroupSpan{f, b};
+                else if (holds_node(nodes, top, g.node)) span.front = kGroupLoose;
+                else if (holds_node(nodes, top, g.node, true) || !holds_node(nodes, root, g.node, true)) {
+                    // (the second test takes ANY group whose node is nowhere in the tree for a look-around's, whatever dropped it.
+                    // That errs to the safe side: such a group only widens rc_max, so a string is decided exactly or the call is
+                    // refused, and a template that refers to it is refused at create -- more OVTK_E_UNSUPPORTED, never other bytes)
+                    // inside a look-around of this alternative -- or of the pattern somewhere: a look-around over one character keeps
+                    // its set alone and the group's node is gone from the tree.  PCRE2 sets the group of a positive look-around that
+                    // held, so it counts for the highest return value; where it lies is not known from the match
+                    if (span.front == kGroupUnset) span.front = kGroupLook;
+                    a.rc_max = std::max(a.rc_max, g.number + 1);
+                    continue;
+                } else continue;
+                a.rc_max = std::max(a.rc_max, g.number + 1);
+                if (span.front >= 0) a.rc_min = std::max(a.rc_min, g.number + 1);
+            }
+            const Node& t = nodes[size_t(top)];
+            const Node& first = t.kind == kCat ? nodes[size_t(t.kids[0])] : t;
+            a.anchored = first.kind == kAssert && first.akind == kBot;
+            if (tops.size() > 1) compile_tree(nodes, top, true, a.prog);
+            out.alts.push_back(std::move(a));
+        }
+        if (tops.size() == 1) out.alts[0].prog = out.whole;
+        return OVTK_OK;
+    } catch (const Unsupported& u) {
+        err = "RegexNormalization: pattern outside the subset compiled for the GPU (" + u.what + "); PCRE2 is not executed on the device";
+        return OVTK_E_UNSUPPORTED;
+    } catch (const Invalid& v) {
+        out = RegexWithGroups{};
         out.invalid = true;
-        out.invalid_why = v.what;
-        out.n_classes = 1;
-        out.sym_eot = 1;
-        out.n_syms = 2;
-        out.n_states = 1;
-        out.trans.assign(2, 0);
-        out.ctx_next.assign(1, 0);
-        out.cp_index.assign((size_t(kMaxCp) + 1) >> 7, 0);
-        out.cp_blocks.assign(128, 0);
+        never_matches(out.whole, v.what);
         return OVTK_OK;
     }
 }

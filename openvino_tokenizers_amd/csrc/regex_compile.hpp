@@ -62,6 +62,10 @@ struct RegexProgram {
     std::vector<uint16_t> cp_index;      // [0x110000 >> 7]
     std::vector<uint8_t> cp_blocks;      // [n_blocks * 128]
     bool can_match_empty = false;        // some start state accepts before consuming anything
+    // compile_regex_groups only: the start states of "the best NON-EMPTY match at this position" (PCRE2_NOTEMPTY_ATSTART |
+    // PCRE2_ANCHORED, what pcre2_substitute asks for behind an empty match): an accept before the first character neither reports nor
+    // cuts the threads behind it.  The states behind them are the ordinary ones.
+    uint16_t start_nonempty[kRegexMaxCtx] = {};
     bool invalid = false;                // PCRE2 itself rejects the pattern: the program never matches (the reference's null pattern,
     std::string invalid_why;             // src/utils.cpp:264-271, 397-399: every string passes through unsplit)
 };
@@ -69,6 +73,32 @@ struct RegexProgram {
 // 0, or OVTK_E_UNSUPPORTED with `err` naming what is outside the subset.  A pattern that PCRE2 itself rejects (an unmatched parenthesis,
 // a quantifier without an operand, a range out of order ...) compiles -- to a program that never matches, RegexProgram::invalid.
 int compile_regex(const std::string& pattern, RegexProgram& out, std::string& err);
+
+// ---- the pattern as RegexNormalization needs it (regex_subst.cpp): the capture groups, and where each one lies inside a match.
+// The DFA yields a match's start and end alone; a group's span is known where it is FIXED relative to them: in front of the group
+// the alternative consumes `front` characters whatever it matches, behind it `back` characters, and the group stands under no
+// quantifier and inside no inner alternation -- the group is [start + front chars, end - back chars).
+constexpr int kGroupUnset = -1;   // the alternative does not hold the group: a match of it leaves the group unset
+constexpr int kGroupLoose = -2;   // it holds the group, but not at a fixed place
+constexpr int kGroupLook = -3;    // the group stands inside a look-around: set when that held, nowhere inside the match
+struct RegexGroupSpan {
+    int front = kGroupUnset, back = 0;
+};
+struct RegexAlternative {
+    RegexProgram prog;                  // the alternative alone (both start tables)
+    std::vector<RegexGroupSpan> groups; // [n_groups + 1], index = group number; [0] = the match
+    int rc_min = 1, rc_max = 1;         // pcre2_match's return value for a match of it: 1 + the highest group set -- between these
+    bool anchored = false;              // starts with `^` / `\A`: can only match at offset 0
+};
+struct RegexWithGroups {
+    bool invalid = false;               // PCRE2 rejects the pattern
+    RegexProgram whole;                 // the whole pattern (both start tables)
+    int n_groups = 0;
+    std::vector<std::pair<std::string, int>> names;
+    std::vector<RegexAlternative> alts; // the top-level alternatives (one entry for a pattern without a top-level `|`)
+};
+// As compile_regex, plus the groups.  compile_regex's result for the same pattern is `whole` without start_nonempty.
+int compile_regex_groups(const std::string& pattern, RegexWithGroups& out, std::string& err);
 
 // General_Category of every code point, as its index in unicode_gc.inc's order (Cn Lu Ll Lt Lm Lo Mn Mc Me Nd Nl No Pc Pd Ps Pe Pi Pf Po
 // Sm Sc Sk So Zs Zl Zp Cc Cf Cs Co): gc[0x110000].  For the class table of span_fam.hpp's scans.

@@ -86,24 +86,32 @@ __device__ __forceinline__ int regex_match_end(uint32_t t, const uint8_t* s, int
     return d == 0 ? i : regex_step_back(s, p, i, d);
 }
 
+// One attempt at position p from DFA state `state` (a start state of the position's context): the end of the match PCRE2 finds there, or
+// -1.  first_len: the bytes of the character at p (0 at the subject's end).
+__device__ __forceinline__ int regex_attempt(const RegexDev& R, const RegexTables& T, const uint8_t* s, int slen, int p, int state, int& first_len) {
+    int i = p, last = -1;
+    first_len = 1;
+    for (;;) {
+        int len = 0;
+        const int sym = i < slen ? regex_symbol(R, T, s, slen, i, len) : R.sym_eot;
+        if (i == p) first_len = len;
+        const uint32_t t = T.trans[state * R.n_syms + sym];
+        if (t & kRegexMatchBit) last = regex_match_end(t, s, p, i);
+        state = int(t & kRegexStateMask);
+        if (state == 0 || i >= slen) break;
+        i += len;
+    }
+    return last;
+}
+
 // The match PCRE2 finds at or after `start` (PCRE2Wrapper::match, src/utils.cpp:396-420): leftmost start position, at
 // that position the first alternative / greediest repetition that lets the whole pattern match.  false: no match.
 __device__ __forceinline__ bool regex_next_match(const RegexDev& R, const RegexTables& T, const uint8_t* s, int slen, int start,
                                                  int& mb, int& me) {
     int p = start;
     while (p <= slen) {
-        int state = R.start[regex_context(R, T, s, slen, p)];
-        int i = p, last = -1, first_len = 1;
-        for (;;) {
-            int len = 0;
-            const int sym = i < slen ? regex_symbol(R, T, s, slen, i, len) : R.sym_eot;
-            if (i == p) first_len = len;
-            const uint32_t t = T.trans[state * R.n_syms + sym];
-            if (t & kRegexMatchBit) last = regex_match_end(t, s, p, i);
-            state = int(t & kRegexStateMask);
-            if (state == 0 || i >= slen) break;
-            i += len;
-        }
+        int first_len = 1;
+        const int last = regex_attempt(R, T, s, slen, p, R.start[regex_context(R, T, s, slen, p)], first_len);
         if (last >= 0) {
             mb = p;
             me = last;

@@ -950,6 +950,61 @@ class CharsMapNormalization(_Op):
         return res + [skips] if skips is not None else res
 
 
+class RegexNormalization(_Op):
+    """Reference: src/regex_normalization.cpp (validate :111-124, evaluate :127-153): pcre2_substitute per string.  Inputs: begins, ends,
+    chars, [skips], search pattern, replace pattern (5 or 6); outputs: begins, ends, chars [+ skips].  The patterns are read at the first
+    evaluate, as the reference's constants are.  Quirks and limits: include/ovtk_amd.h, ovtk_regex_normalization_run."""
+
+    def __init__(self, global_replace=True, device=0, lib=None):
+        super().__init__(device, lib)
+        self.global_replace = bool(global_replace)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ovtk_regex_normalization_destroy(self._h)
+            self._h = None
+
+    def _ensure(self, pattern, replace):
+        if self._h:
+            return
+        pat, rep = _bytes_of(pattern), _bytes_of(replace)
+        p = L.RegexNormalizationParams(pat, len(pat), rep, len(rep), int(self.global_replace), self.device)
+        self._chk(self._lib.ovtk_regex_normalization_create(C.byref(p), C.byref(self._h)))
+
+    def bound(self, n, n_chars):
+        """Bytes the output of n strings of n_chars bytes can take (ovtk_regex_normalization_bound); the handle must exist."""
+        return int(self._lib.ovtk_regex_normalization_bound(self._h, C.c_int64(n), C.c_int64(n_chars)))
+
+    def evaluate(self, inputs, chars_capacity=None):
+        if len(inputs) not in (5, 6):
+            raise L.OvtkError(L.E_ARG, f"supported input sizes are 5 or 6, got{len(inputs)}")   # regex_normalization.cpp:115
+        has_skips = len(inputs) == 6
+        skips = inputs[3] if has_skips else None
+        self._ensure(inputs[3 + has_skips], inputs[4 + has_skips])
+        m = _Mem(inputs[2])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        c, pc = m.inp(inputs[2], "u8")
+        psk = None
+        if has_skips:
+            _, psk = m.inp(skips, "bool")
+        ob, pob = m.alloc(len(b), "i32")
+        oe, poe = m.alloc(len(b), "i32")
+        s = L.Strings(pb, pe, pc, len(b), len(c))
+        # most text grows little: a first buffer of that size, and the size the library reports where it did not do
+        cap = min(self.bound(len(b), len(c)), len(c) + len(c) // 4 + 64) if chars_capacity is None else int(chars_capacity)
+        for attempt in range(2):
+            oc, poc = m.alloc(cap, "u8")
+            out = L.StringsOut(pob, poe, poc, cap, 0)
+            rc = self._lib.ovtk_regex_normalization_run(self._h, C.byref(s), psk, C.byref(out), m.mem, m.stream)
+            if rc != L.E_CAPACITY or chars_capacity is not None or attempt:
+                break
+            cap = int(out.n_chars)
+        self._chk(rc)
+        res = [ob[:len(b)], oe[:len(b)], oc[:out.n_chars]]
+        return res + [skips] if has_skips else res
+
+
 class NormalizeUnicode(CharsMapNormalization):
     """Reference: src/normalize_unicode.cpp (evaluate :32-62): the charsmap of `normalization_form` (NFC, NFD, NFKC, NFKD) with all three
     flags off.  Strings (3) [+ skips] -> strings (3) [+ skips].  `charsmap=`: the form's precompiled table (see CharsMapNormalization)."""

@@ -16,7 +16,7 @@ through the C ABI, one library call per node -- what `core.add_extension()` + th
   Truncate CombineSegments Padding                              -> FusedEncodeTailStep        ovtk_encode_tail_run
   VocabDecoder [ByteFallback] FuzeRagged                        -> FusedDetokenizeStep        ovtk_detokenize_run
 
-and leaves every other step as it is -- the normalizers (CharsmapStep, NormalizeUnicode, CaseFoldStep) among them: a chain behind them
+and leaves every other step as it is -- the normalizers (CharsmapStep, NormalizeUnicode, CaseFoldStep, RegexNormalizationStep) and the detokenizer's RegexDecodingSteps among them: a chain behind them
 is fused as if they were not there.  The rewritten list gives the same outputs as the original one (tests/test_pipeline_fuse.py:
 bit for bit, on BASELINE.json's configurations); adapter/fuse_pass.cpp is the same recogniser over ov::Node chains.
 """
@@ -100,6 +100,120 @@ class CaseFoldStep(_NormalizationStep):
             raise ValueError(f"[ CaseFoldStep ] `encoding` attribute must be one of ['', 'utf-8'], got {encoding!r}.")
         self.encoding = encoding
         self.op = K.CaseFold(encoding=encoding, lower=True, charsmap=charsmap, lib=lib)
+
+
+class RegexNormalizationStep(_NormalizationStep):
+    """src/regex_normalization.cpp:127-153 (tokenizer_pipeline.py:224-289): pcre2_substitute per string, with the reference's
+    constructors by name."""
+
+    def __init__(self, regex_search_pattern, replace_term, global_replace=True, lib=None):
+        self.regex_search_pattern, self.replace_term, self.global_replace = regex_search_pattern, replace_term, bool(global_replace)
+        self.op = K.RegexNormalization(global_replace=self.global_replace, lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "strings"
+        rb, re_, b, e, c = vals[:5]
+        skips = vals[5] if len(vals) > 5 else None
+        out = self.op.evaluate([b, e, c] + ([skips] if skips is not None else []) + [_u8(self.regex_search_pattern), _u8(self.replace_term)])
+        return "strings", [rb, re_] + list(out[:3]) + [skips]
+
+    @classmethod
+    def strip_accents_regex(cls, lib=None):
+        return cls(r"\p{Mn}", "", lib=lib)
+
+    @classmethod
+    def add_prefix_whitespace_regex(cls, lib=None):
+        return cls(r"^(\S)", r" $1", lib=lib)
+
+    @classmethod
+    def replace_whitespace_regex(cls, lib=None):
+        return cls(r"\s", " ", global_replace=True, lib=lib)
+
+    @classmethod
+    def handle_chinese_chars_regex(cls, lib=None):
+        return cls(r"([\p{Han}])", r" $1 ", global_replace=True, lib=lib)
+
+    @classmethod
+    def add_prefix_whitespace_to_not_whitespace_regex(cls, lib=None):
+        return cls(r"^([^ ])", r" $1", lib=lib)
+
+    @classmethod
+    def replace_spaces_metaspace(cls, replace_term="▁", lib=None):
+        return cls(r" ", replace_term, lib=lib)
+
+    @classmethod
+    def prepend_regex(cls, string, lib=None):
+        return cls(r"(?:^)([\s\S])", rf"{string}$1", lib=lib)
+
+    @classmethod
+    def prepend_with_check_regex(cls, string, check_string, lib=None):
+        return cls(rf"(^)([^{check_string}])", rf"{string}$2", lib=lib)
+
+    @classmethod
+    def del_control_chars_regex(cls, lib=None):
+        return cls(r"([\x00-\x08\x0B\x0C\x0E-\x1F\x7F-\x9F\p{Cf}])", "", global_replace=True, lib=lib)   # (\n \t \r stay)
+
+    @classmethod
+    def strip_regex(cls, left=True, right=True, lib=None):
+        return cls(r"^\s*" * left + "|" * (left and right) + r"\s*$" * right, "", lib=lib)
+
+    clean_up_and_remove_extra_whitespaces_regex = strip_regex   # (the strip pattern under the name older converters used)
+
+
+class RegexDecodingStep(Step):
+    """The detokenizer's clean-up steps (tokenizer_pipeline.py:1375-1457): RegexNormalization over the decoded text (always global)."""
+
+    def __init__(self, regex_search_pattern, replace_term, lib=None):
+        self.regex_search_pattern, self.replace_term = regex_search_pattern, replace_term
+        self.op = K.RegexNormalization(global_replace=True, lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind in ("text", "token_strings")
+        ragged = list(vals[:2]) if kind == "token_strings" else []
+        out = self.op.evaluate(list(vals[len(ragged):len(ragged) + 3]) + [_u8(self.regex_search_pattern), _u8(self.replace_term)])
+        return kind, ragged + list(out[:3])
+
+    @classmethod
+    def clean_up_tokenization_spaces(cls, lib=None):
+        return cls(r"(?| ([\\.\\?\\!,])| ('[ms])| (') | ('[rv]e)| (n't))", r"$1", lib=lib)
+
+    @classmethod
+    def parse_replace_dict(cls, replace_dict, lib=None):
+        pattern, content = replace_dict.get("pattern", {}).get("String"), replace_dict.get("content")
+        if pattern is None or content is None:
+            raise ValueError(f"Replace Decoding Op with this parameters: `{replace_dict}` does not support yet.")
+        return cls(pattern, content, lib=lib)
+
+    @classmethod
+    def parse_strip_dict(cls, replace_dict, lib=None):
+        content = replace_dict.get("content")
+        if content is None:
+            raise ValueError(f"Replace Decoding Op with this parameters: `{replace_dict}` does not support yet.")
+        return cls(f"^{content}", "", lib=lib)
+
+    @classmethod
+    def rstrip_space(cls, lib=None):
+        return cls(r" $", "", lib=lib)
+
+    @classmethod
+    def strip_forward_space(cls, lib=None):
+        return cls(r"^ ", "", lib=lib)
+
+    @classmethod
+    def strip_forward_space_before_not_space(cls, lib=None):
+        return cls(r"(^ )([^ ])", r"$2", lib=lib)
+
+    @classmethod
+    def replace_end_of_word_suffix(cls, suffix="</w>", lib=None):
+        return cls(suffix, " ", lib=lib)
+
+    @classmethod
+    def replace_continuing_subword_prefix(cls, prefix="##", lib=None):
+        return cls(prefix, "", lib=lib)
+
+    @classmethod
+    def replace_sp_spaces(cls, lib=None):
+        return cls("▁", " ", lib=lib)
 
 
 class SpecialTokensSplitStep(Step):

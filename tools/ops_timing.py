@@ -3,7 +3,7 @@ on a config-2-shaped batch (65 536 rows x ~512 bytes of zipf text, a GPT-2 speci
 batch for the ops behind the tokenizer), inputs and outputs in HBM:
 
     UTF8Validate (both modes), SpecialTokensSplit (the op: count pass, scan, write pass), RegexSplit (the op), StringTensorPack /
-    StringTensorUnpack, TrieTokenizer, UnigramTokenizer, CharsMapNormalization, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
+    StringTensorUnpack, TrieTokenizer, UnigramTokenizer, CharsMapNormalization, RegexNormalization, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
     (ovtk_encode_tail_run: Truncate -> CombineSegments -> RaggedToDense x 2 in one call).
 
 Per op one JSON line: wall time per call (Python + the library's host side + the kernels; the call returns when its results are
@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
 from pathlib import Path
@@ -193,6 +194,42 @@ def main():
                        n_c + 16 * n + int(n_c * 1.03), lambda out, ref_cm=ref_cm: same(ref_cm[:2], [to_np(out[0])[:k], to_np(out[1])[:k]]) and same([ref_cm[2]], [to_np(out[2])], upto=len(ref_cm[2])),
                        "a wave per row counts, a scan, a wave per row writes: the trie is walked twice")
         del cm_out
+    # ---- RegexNormalization (src/regex_normalization.cpp:127-153): BERT's four regex normalizers (tokenizer_pipeline.py:224-278) and the
+    # detokenizer's clean-up pattern (:1380-1384) on the same batch -- ASCII zipf text: `\s` and the clean-up pattern find matches in it,
+    # the control-character, Han and \p{Mn} patterns find none (their figures are the no-match case).  The class-path patterns run
+    # again with OVTK_REGEX_NORM_GENERAL=1; the check and the CPU baseline are tests/pcre2_substitute.py (one core) on the first rows
+    from openvino_tokenizers_amd.ops import RegexNormalization
+    from openvino_tokenizers_amd.pipeline import RegexDecodingStep, RegexNormalizationStep
+    from tests.pcre2_substitute import normalize as pcre2_normalize
+
+    class _Spec:
+        def __init__(self, regex_search_pattern, replace_term, global_replace=True, lib=None):
+            self.args = (regex_search_pattern, replace_term, global_replace)
+    head_strings = [bytes(c[int(b[i]):int(e[i])]) for i in range(k)]
+    knob = os.environ.get("OVTK_REGEX_NORM_GENERAL")
+    for label, cls, ctor, class_path in (("\\s -> ' '", RegexNormalizationStep, "replace_whitespace_regex", True),
+                                         ("control characters deleted", RegexNormalizationStep, "del_control_chars_regex", True),
+                                         ("Han isolated", RegexNormalizationStep, "handle_chinese_chars_regex", True),
+                                         ("\\p{Mn} deleted", RegexNormalizationStep, "strip_accents_regex", True),
+                                         ("clean_up_tokenization_spaces", RegexDecodingStep, "clean_up_tokenization_spaces", False)):
+        pattern, replace, g = getattr(cls, ctor).__func__(_Spec).args
+        t0 = time.perf_counter()
+        ref_rn = pcre2_normalize(head_strings, pattern, replace, g)
+        cpu_ms = (time.perf_counter() - t0) * 1e3
+        cpu_bytes = sum(len(x) for x in head_strings)
+        consts = [np.frombuffer(pattern.encode(), np.uint8), np.frombuffer(replace.encode(), np.uint8)]
+        for forced in (("", "1") if class_path else ("",)):
+            os.environ["OVTK_REGEX_NORM_GENERAL"] = forced
+            rn = RegexNormalization(g, lib=lib)
+            rn._ensure(*consts)   # (the knob is read at create)
+            if knob is None:
+                del os.environ["OVTK_REGEX_NORM_GENERAL"]
+            else:
+                os.environ["OVTK_REGEX_NORM_GENERAL"] = knob
+            path = "general path forced" if forced else ("class path" if class_path else "general path")
+            timed(f"RegexNormalization({label}, {path})", lambda rn=rn: rn.evaluate(d[2:5] + consts), 2 * n_c + 16 * n,
+                  lambda out: same(ref_rn[:2], [to_np(out[0])[:k], to_np(out[1])[:k]]) and same([ref_rn[2]], [to_np(out[2])], upto=len(ref_rn[2])),
+                  f"count -> scan -> write; PCRE2 on one core: {cpu_ms:.2f} ms for the first {k} rows ({cpu_bytes / cpu_ms / 1e6:.3f} GB/s)")
     # ---- the ids of the batch (the fused encode), then the ops behind the tokenizer
     fused = FusedSplitBPE(RegexSplit("isolate", lib=lib), BPETokenizer(**tok.attrs, lib=lib))
     ib, ie, ids = fused.evaluate(d + [pat], tok.consts)
