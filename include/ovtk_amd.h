@@ -546,6 +546,50 @@ int ovtk_regex_normalization_run(ovtk_regex_normalization* h, const ovtk_strings
 int64_t ovtk_regex_normalization_bound(ovtk_regex_normalization* h, int64_t n, int64_t n_chars);
 void ovtk_regex_normalization_destroy(ovtk_regex_normalization* h);
 
+/* ---------------------------------------------------------------- SentencepieceTokenizer (unigram models) / RaggedToSparse
+ * ovtk_sentencepiece_run replaces SentencepieceTokenizer::evaluate, src/sentence_piece.cpp:188-350, in its 4-input form (sp model,
+ * begins, ends, chars): per sentence SentencePieceProcessor::Encode with the extra options of :58-73, then the sparse outputs of
+ * :331-347.  `model`: a serialized sentencepiece ModelProto, host memory, consumed at create (the reference's lazy init, :193-198);
+ * a truncated or malformed buffer, or a model sentencepiece itself refuses to load, is OVTK_E_ARG.  Bit-exact with sentencepiece's
+ * optimized unigram encoder: the sentence is normalized whole by the model's normalizer_spec (ovtk_charsmap_*, with its refusals), the
+ * best path is searched over the whole normalized sentence (ovtk_unigram_*'s lattice: float32 sums, strict >, an unknown edge of
+ * min_score - 10 with min_score over the NORMAL pieces); CONTROL, UNKNOWN and BYTE pieces are never matched by text; an UNUSED piece
+ * is never a candidate; a run of unknown pieces is one unk id, or -- trainer_spec.byte_fallback -- every unknown piece becomes the id
+ * of <0xHH> for each of its bytes; add_bos / add_eos put the model's bos / eos id in front / behind, also around an empty sentence;
+ * reverse alone reverses the row.
+ * OVTK_E_UNSUPPORTED at create, never an approximation: a model_type other than UNIGRAM, treat_whitespace_as_suffix, USER_DEFINED
+ * pieces, a piece longer than 1 023 bytes, 4 194 303 or more pieces, nbest_size other than 0 or 1 (sampling), reverse together with
+ * add_bos or add_eos (the outcome depends on the order of the extra options), add_bos / add_eos with a model that has no such piece.
+ * out: indices i64 [n][2] = (row, position) in row order, values i32 [n], dense_shape i64 [2] = {rows, longest row}; buffers of
+ * `capacity` ids.  ovtk_sentencepiece_bound(h, n, n_chars) is an upper bound of the ids for any input of n sentences and n_chars
+ * bytes; a smaller buffer is fine when the ids fit: OVTK_E_CAPACITY otherwise, out->n = the ids the call needs, nothing written.
+ * With OVTK_MEM_DEVICE `indices` must be 16-byte aligned.
+ * ovtk_ragged_to_sparse replaces RaggedToSparse::evaluate, src/ragged_to_sparse.cpp:27-47: out i32 [n][2] = (row, position) for
+ * every element of every row, *n_out = the sum of the rows' lengths (the reference sizes its output ends[last] - begins[0], the same
+ * number where the rows are back to back); a row that ends before it begins is OVTK_E_RANGE.  Stateless. */
+typedef struct ovtk_sentencepiece ovtk_sentencepiece;
+typedef struct ovtk_sentencepiece_params {
+    int32_t nbest_size;
+    float alpha; /* stored; only sampling would read it */
+    int add_bos;
+    int add_eos;
+    int reverse;
+    int device;
+} ovtk_sentencepiece_params;
+typedef struct ovtk_sparse_i32_out {
+    int64_t* indices;     /* [capacity][2] */
+    int32_t* values;      /* [capacity] */
+    int64_t* dense_shape; /* [2] */
+    int64_t capacity;
+    int64_t n; /* out: ids written (OVTK_E_CAPACITY: ids needed) */
+} ovtk_sparse_i32_out;
+int ovtk_sentencepiece_create(const uint8_t* model, int64_t model_len, const ovtk_sentencepiece_params* params, ovtk_sentencepiece** out);
+int ovtk_sentencepiece_run(ovtk_sentencepiece* h, const ovtk_strings* in, ovtk_sparse_i32_out* out, int mem, void* stream);
+int64_t ovtk_sentencepiece_bound(ovtk_sentencepiece* h, int64_t n, int64_t n_chars);
+void ovtk_sentencepiece_destroy(ovtk_sentencepiece* h);
+int ovtk_ragged_to_sparse(const int32_t* begins, const int32_t* ends, int64_t n_rows, int32_t* out, int64_t capacity, int64_t* n_out, int mem,
+                          int device, void* stream);
+
 /* ---------------------------------------------------------------- UTF8Validate
  * Replaces UTF8Validate::evaluate, src/utf8_validate.cpp:18-143.  replace_mode 0: drop invalid bytes, 1: U+FFFD.
  * out->begins/ends: [in->n]; out->chars capacity: the reference allocates 3 * in->n_chars (:31-33).  Offsets start

@@ -82,6 +82,15 @@ class RegexNormalizationParams(C.Structure):
                 ("global_replace", C.c_int), ("device", C.c_int)]
 
 
+class SentencepieceParams(C.Structure):
+    _fields_ = [("nbest_size", C.c_int32), ("alpha", C.c_float), ("add_bos", C.c_int), ("add_eos", C.c_int), ("reverse", C.c_int),
+                ("device", C.c_int)]
+
+
+class SparseI32Out(C.Structure):
+    _fields_ = [("indices", C.c_void_p), ("values", C.c_void_p), ("dense_shape", C.c_void_p), ("capacity", C.c_int64), ("n", C.c_int64)]
+
+
 class StringsOut(C.Structure):
     _fields_ = [("begins", C.c_void_p), ("ends", C.c_void_p), ("chars", C.c_void_p), ("chars_capacity", C.c_int64),
                 ("n_chars", C.c_int64)]
@@ -122,6 +131,7 @@ EXPORTS = [
     "ovtk_unigram_create", "ovtk_unigram_run", "ovtk_unigram_destroy",
     "ovtk_charsmap_create", "ovtk_charsmap_run", "ovtk_charsmap_bound", "ovtk_charsmap_destroy", "ovtk_case_fold_ascii",
     "ovtk_regex_normalization_create", "ovtk_regex_normalization_run", "ovtk_regex_normalization_bound", "ovtk_regex_normalization_destroy",
+    "ovtk_sentencepiece_create", "ovtk_sentencepiece_run", "ovtk_sentencepiece_bound", "ovtk_sentencepiece_destroy", "ovtk_ragged_to_sparse",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -169,6 +179,14 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_charsmap_bound.restype = C.c_int64
     lib.ovtk_charsmap_destroy.argtypes = [C.c_void_p]
     lib.ovtk_charsmap_destroy.restype = None
+    lib.ovtk_sentencepiece_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(SentencepieceParams), C.POINTER(C.c_void_p)]
+    lib.ovtk_sentencepiece_run.argtypes = [C.c_void_p, C.POINTER(Strings), C.POINTER(SparseI32Out), C.c_int, C.c_void_p]
+    lib.ovtk_sentencepiece_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+    lib.ovtk_sentencepiece_bound.restype = C.c_int64
+    lib.ovtk_sentencepiece_destroy.argtypes = [C.c_void_p]
+    lib.ovtk_sentencepiece_destroy.restype = None
+    lib.ovtk_ragged_to_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int, C.c_int,
+                                          C.c_void_p]
     lib.ovtk_case_fold_ascii.argtypes = [C.POINTER(Strings), C.c_int, C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
     lib.ovtk_regex_normalization_create.argtypes = [C.POINTER(RegexNormalizationParams), C.POINTER(C.c_void_p)]
     lib.ovtk_regex_normalization_run.argtypes = [C.c_void_p, C.POINTER(Strings), C.c_void_p, C.POINTER(StringsOut), C.c_int, C.c_void_p]

@@ -9,18 +9,12 @@
 #include <vector>
 
 #include "api_common.hpp"
+#include "charsmap_handle.hpp"
 #include "charsmap_kernels.hpp"
 #include "ops_kernels.hpp"
 #include "runtime.hpp"
 
 using namespace ovtk;
-
-struct ovtk_charsmap {
-    int device = 0;
-    CharsmapDev dev{};
-    DevBuf units, strings, meta;
-    int64_t per_byte = 3;   // output bytes an input byte can become
-};
 
 namespace {
 

@@ -1005,6 +1005,84 @@ class RegexNormalization(_Op):
         return res + [skips] if has_skips else res
 
 
+class SentencepieceTokenizer(_Op):
+    """Reference: src/sentence_piece.cpp (evaluate :188-350), for unigram models.  Inputs: sp_model u8 (a serialized sentencepiece
+    ModelProto, read at the first evaluate), begins, ends, chars.  Outputs: indices i64 [n, 2], values i32 [n], dense_shape i64 [2].
+    Attributes and their defaults as the reference's factory gives them (src/tokenizers_factory.cpp:61-67).  What is refused, and
+    why: include/ovtk_amd.h, ovtk_sentencepiece_run."""
+
+    def __init__(self, nbest_size=0, alpha=0.0, add_bos=False, add_eos=False, reverse=False, device=0, lib=None):
+        super().__init__(device, lib)
+        self.nbest_size, self.alpha = int(nbest_size), float(alpha)
+        self.add_bos, self.add_eos, self.reverse = bool(add_bos), bool(add_eos), bool(reverse)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ovtk_sentencepiece_destroy(self._h)
+            self._h = None
+
+    def _ensure(self, model):
+        if self._h:
+            return
+        buf = np.frombuffer(_bytes_of(model), np.uint8)
+        p = L.SentencepieceParams(self.nbest_size, self.alpha, int(self.add_bos), int(self.add_eos), int(self.reverse), self.device)
+        self._chk(self._lib.ovtk_sentencepiece_create(buf.ctypes.data_as(C.c_void_p) if len(buf) else None, C.c_int64(len(buf)), C.byref(p),
+                                                      C.byref(self._h)))
+
+    def bound(self, n, n_chars):
+        """Ids that n sentences of n_chars bytes can give (ovtk_sentencepiece_bound); the handle must exist (after a first evaluate)."""
+        return int(self._lib.ovtk_sentencepiece_bound(self._h, C.c_int64(n), C.c_int64(n_chars)))
+
+    def evaluate(self, inputs, capacity=None):
+        if len(inputs) in (2, 6):   # sentence_piece.cpp:153-157, :257-264: the element::string container stays with the caller
+            raise L.OvtkError(L.E_ARG, "SentencepieceTokenizer: string-tensor inputs are a host container; unpack them first "
+                                       "(StringTensorUnpack) and pass sp_model, begins, ends, chars")
+        if len(inputs) == 8:
+            raise L.OvtkError(L.E_UNSUPPORTED, "SentencepieceTokenizer: the 8-input form (special tokens split off by a regex, "
+                                               "sentence_piece.cpp:200-230, :286-329) is a follow-up; pass sp_model, begins, ends, chars")
+        if len(inputs) != 4:
+            raise L.OvtkError(L.E_ARG, "Unexpected input format. SentencepieceTokenizer accepts one string input or three decomposed "
+                                       "string inputs (begins, ends, symbols)")   # :162
+        self._ensure(inputs[0])
+        m = _Mem(inputs[3])
+        b, pb = m.inp(inputs[1], "i32")
+        e, pe = m.inp(inputs[2], "i32")
+        c, pc = m.inp(inputs[3], "u8")
+        s = L.Strings(pb, pe, pc, len(b), len(c))
+        shape, pshape = m.alloc(2, "i64")
+        # a sentence gives far fewer ids than it has bytes: a first buffer of that size, and the size the library reports otherwise
+        cap = min(self.bound(len(b), len(c)), len(c) + 4 * len(b) + 64) if capacity is None else int(capacity)
+        for attempt in range(2):
+            idx, pidx = m.alloc(2 * cap, "i64")
+            val, pval = m.alloc(cap, "i32")
+            out = L.SparseI32Out(pidx, pval, pshape, cap, 0)
+            rc = self._lib.ovtk_sentencepiece_run(self._h, C.byref(s), C.byref(out), m.mem, m.stream)
+            if rc != L.E_CAPACITY or capacity is not None or attempt:
+                break
+            cap = int(out.n)
+        self._chk(rc)
+        return [idx[:2 * out.n].reshape(-1, 2), val[:out.n], shape[:2]]
+
+
+class RaggedToSparse(_Op):
+    """Reference: src/ragged_to_sparse.cpp (evaluate :27-47).  Inputs: begins, ends (i32).  Output: i32 [n, 2], (row, position) of
+    every element of every row."""
+
+    def evaluate(self, inputs):
+        if len(inputs) != 2:
+            raise L.OvtkError(L.E_ARG, f"RaggedToSparse takes begins and ends, got {len(inputs)} inputs")   # :14
+        m = _Mem(inputs[0])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        if len(b) != len(e):
+            raise L.OvtkError(L.E_ARG, "starts and ends tensors should be the same shape.")   # :21
+        total = int((e.long() - b).clamp(min=0).sum()) if m.torch else int(np.maximum(e.astype(np.int64) - b, 0).sum())
+        out, pout = m.alloc(2 * total, "i32")
+        n = C.c_int64(0)
+        self._chk(self._lib.ovtk_ragged_to_sparse(pb, pe, C.c_int64(len(b)), pout, C.c_int64(total), C.byref(n), m.mem, self.device, m.stream))
+        return [out[:2 * n.value].reshape(-1, 2)]
+
+
 class NormalizeUnicode(CharsMapNormalization):
     """Reference: src/normalize_unicode.cpp (evaluate :32-62): the charsmap of `normalization_form` (NFC, NFD, NFKC, NFKD) with all three
     flags off.  Strings (3) [+ skips] -> strings (3) [+ skips].  `charsmap=`: the form's precompiled table (see CharsMapNormalization)."""

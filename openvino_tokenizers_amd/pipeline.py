@@ -287,6 +287,39 @@ class UnigramModelStep(Step):
         return "ids", self.op.evaluate(list(vals[:5]) + self.consts)
 
 
+class SentencepieceModelStep(Step):
+    """src/sentence_piece.cpp:188-350 and what python/openvino_tokenizers/hf_parser.py:879-911 puts behind it: the op's sparse ids,
+    then two ScatterNDUpdates -- the ids into a [batch, longest row] tensor of `pad_id`, ones into an attention mask of zeros.
+    `model`: the serialized sentencepiece model.  The op takes whole sentences: a row of the state is one string (as behind
+    StringTensorUnpack), and a state that carries skips is refused as UnigramModelStep refuses it.  The scatter is plain tensor
+    indexing next to the op's outputs; it is no hot path."""
+
+    def __init__(self, model, add_bos=False, add_eos=False, reverse=False, pad_id=0, nbest_size=1, alpha=1.0, lib=None):
+        self.model = np.frombuffer(bytes(model), np.uint8)
+        self.pad_id = int(pad_id)
+        self.op = K.SentencepieceTokenizer(nbest_size=nbest_size, alpha=alpha, add_bos=add_bos, add_eos=add_eos, reverse=reverse, lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "strings"
+        if len(vals) > 5 and vals[5] is not None:
+            raise ValueError("SentencepieceModelStep: the state carries skips (a SpecialTokensSplit in front), and the 4-input "
+                             "SentencepieceTokenizer has no skips input")
+        b, e, c = vals[2:5]
+        indices, values, dense_shape = self.op.evaluate([self.model, b, e, c])
+        if _is_torch(values):
+            import torch
+            shape = [int(x) for x in dense_shape.cpu()]
+            ids = torch.full(shape, self.pad_id, dtype=torch.int32, device=values.device)
+            mask = torch.zeros(shape, dtype=torch.int32, device=values.device)
+        else:
+            shape = [int(x) for x in dense_shape]
+            ids = np.full(shape, self.pad_id, np.int32)
+            mask = np.zeros(shape, np.int32)
+        ids[indices[:, 0], indices[:, 1]] = values
+        mask[indices[:, 0], indices[:, 1]] = 1
+        return "dense", [ids, mask]
+
+
 class TruncationStep(Step):
     """src/truncate.cpp:37-150, one input."""
 

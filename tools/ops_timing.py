@@ -2,6 +2,8 @@
 on a config-2-shaped batch (65 536 rows x ~512 bytes of zipf text, a GPT-2 special token in one row in a hundred; the ids of that
 batch for the ops behind the tokenizer), inputs and outputs in HBM:
 
+    SentencepieceTokenizer (a fixture unigram model; beside it CharsMapNormalization followed by UnigramTokenizer on whole rows with the
+    model's charsmap and pieces, the two calls the one call replaces; --only-sentencepiece stops behind these rows),
     UTF8Validate (both modes), SpecialTokensSplit (the op: count pass, scan, write pass), RegexSplit (the op), StringTensorPack /
     StringTensorUnpack, TrieTokenizer, UnigramTokenizer, CharsMapNormalization, RegexNormalization, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
     (ovtk_encode_tail_run: Truncate -> CombineSegments -> RaggedToDense x 2 in one call).
@@ -11,7 +13,7 @@ complete, so host waits are inside), the algorithmic bytes the op has to move (i
 they make, and whether a prefix of the result equals the oracle's.  The kernels' own durations: run this script under
 `rocprofv3 --kernel-trace --stats` (profiles/README.md); VERDICT r04 weak 6 asked for both.
 
-    python tools/ops_timing.py [--rows 65536] [--bytes 512] [--reps 10] [--check-rows 256]
+    python tools/ops_timing.py [--rows 65536] [--bytes 512] [--reps 10] [--check-rows 256] [--only-sentencepiece]
 """
 from __future__ import annotations
 
@@ -27,12 +29,56 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 
+def _proto_fields(buf):
+    """(field, wire type, value) of one protobuf message; the value of a length-delimited field is its bytes."""
+    at = 0
+
+    def varint():
+        nonlocal at
+        v = shift = 0
+        while True:
+            x = buf[at]
+            at += 1
+            v |= (x & 0x7F) << shift
+            shift += 7
+            if not x & 0x80:
+                return v
+    while at < len(buf):
+        tag = varint()
+        wt = tag & 7
+        if wt == 0:
+            val = varint()
+        elif wt == 2:
+            ln = varint()
+            val = bytes(buf[at:at + ln])
+            at += ln
+        else:
+            ln = 8 if wt == 1 else 4
+            val = bytes(buf[at:at + ln])
+            at += ln
+        yield tag >> 3, wt, val
+
+
+def sp_model_tables(model):
+    """A sentencepiece ModelProto's pieces, scores and precompiled charsmap (what csrc/sp_model.hpp reads, for the two-call baseline)."""
+    pieces, scores, blob = [], [], b""
+    for f, _, v in _proto_fields(bytes(model)):
+        if f == 1:
+            d = {ff: vv for ff, _, vv in _proto_fields(v)}
+            pieces.append(d.get(1, b""))
+            scores.append(np.frombuffer(d.get(2, bytes(4)), np.float32)[0])
+        elif f == 3:
+            blob = {ff: vv for ff, _, vv in _proto_fields(v)}.get(2, b"")
+    return pieces, np.array(scores, np.float32), blob
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=65536)
     ap.add_argument("--bytes", type=int, default=512)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--check-rows", type=int, default=256)
+    ap.add_argument("--only-sentencepiece", action="store_true", help="the SentencepieceTokenizer rows and nothing else")
     ap.add_argument("--emu", action="store_true", help="the SIMT-emulator build on host arrays (a smoke test of this script; the times mean nothing)")
     args = ap.parse_args()
     from openvino_tokenizers_amd import _lib as L
@@ -94,6 +140,32 @@ def main():
         return out
 
     n_c = len(c)
+    # ---- SentencepieceTokenizer (src/sentence_piece.cpp:188-350), the fixture unigram model with the nmt_nfkc charsmap: one call; beside
+    # it the two calls it replaces, CharsMapNormalization then UnigramTokenizer over whole rows with the model's own tables (three
+    # rounds of each, alternating: the spread of the pair is the yardstick for the one call).  The check: the one call's ids are the
+    # pair's on the first rows (this text has no character the two treat differently).
+    from openvino_tokenizers_amd.ops import CharsMapNormalization, SentencepieceTokenizer, UnigramTokenizer
+    sp_model = np.frombuffer((Path(__file__).resolve().parent.parent / "tests" / "golden" / "spm_unigram_nfkc.model").read_bytes(), np.uint8)
+    sp_pieces, sp_scores, sp_blob = sp_model_tables(sp_model)
+    spb, spe, spc = pack_strings(sp_pieces)
+    sp_op = SentencepieceTokenizer(lib=lib)
+    sp_cm = CharsMapNormalization(True, True, True, charsmap=sp_blob, lib=lib)
+    sp_uni = UnigramTokenizer(unk_token_id=0, lib=lib)
+
+    def sp_pair():
+        nb, ne, nc = sp_cm.evaluate(d[2:5])
+        return sp_uni.evaluate([d[0], d[1], nb, ne, nc, spb, spe, spc, sp_scores])
+    pair_head = [to_np(x) for x in sp_pair()]
+    n_ids = int(len(pair_head[2]))
+    head_ids = pair_head[2][:int(pair_head[1][k - 1])]
+    for trial in range(3):
+        timed(f"CharsMapNormalization + UnigramTokenizer (whole rows, spm_unigram_nfkc), round {trial}", sp_pair, 3 * n_c + 32 * n + 4 * n_ids, None,
+              "two calls, the normalized text and a host wait in between")
+        timed(f"SentencepieceTokenizer(spm_unigram_nfkc), round {trial}", lambda: sp_op.evaluate([sp_model] + d[2:5]), n_c + 8 * n + 20 * n_ids,
+              lambda out: same([head_ids], [to_np(out[1])], upto=len(head_ids)) and int(to_np(out[2])[0]) == n,
+              f"{n_ids} ids: normalize (count, scan, write) -> edges -> relax -> scan -> sparse writer, one enqueue sequence")
+    if args.only_sentencepiece:
+        return
     # ---- UTF8Validate (src/utf8_validate.cpp:18-143): strings in, strings out
     for mode in (False, True):
         op = UTF8Validate(replace_mode=mode, lib=lib)
