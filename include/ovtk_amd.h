@@ -660,6 +660,37 @@ int ovtk_detokenize_enqueue(ovtk_vocab_decoder* h, const int32_t* ids, int64_t b
                             int64_t n_skip_in, int byte_fallback, ovtk_strings_out* out, void* stream, ovtk_pending** pending);
 int ovtk_detokenize_finish(ovtk_pending* pending, ovtk_strings_out* out);
 
+/* ---------------------------------------------------------------- SentencepieceDetokenizer / SentencepieceStreamDetokenizer
+ * ovtk_sp_detokenizer_run replaces SentencepieceDetokenizer::evaluate, src/sentence_piece.cpp:395-433 (stream_mode 0), and
+ * SentencepieceStreamDetokenizer::evaluate, :478-523 (stream_mode 1): ids i32 [batch, seq_len] -> one string per row, rows back to
+ * back from 0, int32 offsets.  Ids >= the model's piece count are dropped (:412-420, :503-505); a negative id is OVTK_E_RANGE for
+ * the call with nothing written (Decode fails with OUT_OF_RANGE, the reference's CHECK_OK throws).
+ * stream_mode 0 is SentencePieceProcessor::Decode over the remaining ids, whatever the model's type: CONTROL pieces give nothing;
+ * the UNKNOWN piece gives trainer_spec.unk_surface (absent: " \xE2\x81\x87 "); every other non-BYTE piece gives its text with each
+ * U+2581 as one space; at the start of a sentence (normalizer_spec.add_dummy_prefix or remove_extra_whitespaces) one leading U+2581
+ * is dropped -- with remove_extra_whitespaces from every piece until something non-empty came out, else from the first piece that
+ * is no CONTROL piece; a maximal run of BYTE pieces is decoded as UTF-8, every byte that is not part of a well-formed character
+ * becomes U+FFFD; any other piece ends a run, a dropped id does not.
+ * stream_mode 1 copies every piece as it is; a piece of six bytes of the shape <0x..> becomes the one byte PieceToByte gives.
+ * ovtk_sp_detokenizer_create: `model` is a serialized sentencepiece ModelProto, host memory, consumed here; a truncated or malformed
+ * buffer is OVTK_E_ARG as for ovtk_sentencepiece_create.  OVTK_E_UNSUPPORTED at create, never an approximation:
+ * treat_whitespace_as_suffix, a non-empty denormalizer_spec.precompiled_charsmap, a piece or unk_surface longer than 1 023 bytes, an unk_surface that is present and empty,
+ * 4 194 303 or more pieces.  OVTK_E_UNSUPPORTED from a stream_mode 1 call (not at create): a model with a piece of the shape
+ * <0x..> whose two middle characters are not upper-case hex digits.
+ * The capacity protocol is ovtk_detokenize_run's: a call whose text does not fit out->chars_capacity returns OVTK_E_CAPACITY with
+ * out->n_chars = the bytes it needs and nothing written.  ovtk_sp_detokenizer_bound(h, batch, seq_len) bytes suffice for any ids:
+ * per token the largest of the longest piece, 3 and the unknown surface.  _enqueue / _finish are the call in two halves for device
+ * buffers, as ovtk_detokenize_enqueue / ovtk_detokenize_finish. */
+typedef struct ovtk_sp_detokenizer ovtk_sp_detokenizer;
+int ovtk_sp_detokenizer_create(const uint8_t* model, int64_t model_len, int device, ovtk_sp_detokenizer** out);
+int ovtk_sp_detokenizer_run(ovtk_sp_detokenizer* h, const int32_t* ids, int64_t batch, int64_t seq_len, int stream_mode, ovtk_strings_out* out,
+                            int mem, void* stream);
+int64_t ovtk_sp_detokenizer_bound(ovtk_sp_detokenizer* h, int64_t batch, int64_t seq_len);
+void ovtk_sp_detokenizer_destroy(ovtk_sp_detokenizer* h);
+int ovtk_sp_detokenizer_enqueue(ovtk_sp_detokenizer* h, const int32_t* ids, int64_t batch, int64_t seq_len, int stream_mode, ovtk_strings_out* out,
+                                void* stream, ovtk_pending** pending);
+int ovtk_sp_detokenizer_finish(ovtk_pending* pending, ovtk_strings_out* out);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py)
  * With profiling on, every kernel launch of the library is bracketed by hipEvents on the stream it is
  * launched on; times are accumulated per kernel name after the call's own synchronisation. */

@@ -7,4 +7,4 @@ include/ovtk_amd.h; see DESIGN.md and INTEGRATION.md.
 """
 from ._lib import OvtkError, load  # noqa: F401
 from .ops import (BPETokenizer, ByteFallback, CaseFold, CharsMapNormalization, CombineSegments, FusedDetokenizer, FusedEncodeDense, FusedEncodeTail, FusedSpecialSplitBPE, FusedSplitBPE, FusedSplitWordpiece, FuzeRagged, NormalizeUnicode, RaggedToDense, RaggedToSparse,  # noqa: F401
-                  RegexNormalization, RegexSplit, SentencepieceTokenizer, SpecialTokensSplit, StringTensorPack, StringTensorUnpack, TrieTokenizer, Truncate, UnigramTokenizer, UTF8Validate, VocabDecoder, VocabEncoder, WordpieceTokenizer)
+                  RegexNormalization, RegexSplit, SentencepieceDetokenizer, SentencepieceStreamDetokenizer, SentencepieceTokenizer, SpecialTokensSplit, StringTensorPack, StringTensorUnpack, TrieTokenizer, Truncate, UnigramTokenizer, UTF8Validate, VocabDecoder, VocabEncoder, WordpieceTokenizer)

@@ -132,6 +132,8 @@ EXPORTS = [
     "ovtk_charsmap_create", "ovtk_charsmap_run", "ovtk_charsmap_bound", "ovtk_charsmap_destroy", "ovtk_case_fold_ascii",
     "ovtk_regex_normalization_create", "ovtk_regex_normalization_run", "ovtk_regex_normalization_bound", "ovtk_regex_normalization_destroy",
     "ovtk_sentencepiece_create", "ovtk_sentencepiece_run", "ovtk_sentencepiece_bound", "ovtk_sentencepiece_destroy", "ovtk_ragged_to_sparse",
+    "ovtk_sp_detokenizer_create", "ovtk_sp_detokenizer_run", "ovtk_sp_detokenizer_bound", "ovtk_sp_detokenizer_destroy",
+    "ovtk_sp_detokenizer_enqueue", "ovtk_sp_detokenizer_finish",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -187,6 +189,15 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_sentencepiece_destroy.restype = None
     lib.ovtk_ragged_to_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int, C.c_int,
                                           C.c_void_p]
+    lib.ovtk_sp_detokenizer_create.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ovtk_sp_detokenizer_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(StringsOut), C.c_int, C.c_void_p]
+    lib.ovtk_sp_detokenizer_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+    lib.ovtk_sp_detokenizer_bound.restype = C.c_int64
+    lib.ovtk_sp_detokenizer_destroy.argtypes = [C.c_void_p]
+    lib.ovtk_sp_detokenizer_destroy.restype = None
+    lib.ovtk_sp_detokenizer_enqueue.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(StringsOut), C.c_void_p,
+                                                C.POINTER(C.c_void_p)]
+    lib.ovtk_sp_detokenizer_finish.argtypes = [C.c_void_p, C.POINTER(StringsOut)]
     lib.ovtk_case_fold_ascii.argtypes = [C.POINTER(Strings), C.c_int, C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
     lib.ovtk_regex_normalization_create.argtypes = [C.POINTER(RegexNormalizationParams), C.POINTER(C.c_void_p)]
     lib.ovtk_regex_normalization_run.argtypes = [C.c_void_p, C.POINTER(Strings), C.c_void_p, C.POINTER(StringsOut), C.c_int, C.c_void_p]

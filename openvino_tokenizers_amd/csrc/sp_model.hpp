@@ -1,9 +1,9 @@
 // sp_model.hpp -- the fields of a serialized SentencePiece ModelProto that SentencepieceTokenizer needs, read straight off the
 // protobuf wire format (host code, no protobuf library, no HIP).  What sentencepiece_model.proto declares:
-//   ModelProto      1 pieces (repeated message)   2 trainer_spec   3 normalizer_spec
+//   ModelProto      1 pieces (repeated message)   2 trainer_spec   3 normalizer_spec   5 denormalizer_spec (a NormalizerSpec)
 //   SentencePiece   1 piece (string)   2 score (float)   3 type (enum, default NORMAL)
 //   TrainerSpec     3 model_type (enum, default UNIGRAM)   24 treat_whitespace_as_suffix   35 byte_fallback
-//                   40 unk_id (0)   41 bos_id (1)   42 eos_id (2)   45 unk_piece   46 bos_piece ("<s>")   47 eos_piece ("</s>")
+//                   40 unk_id (0)   41 bos_id (1)   42 eos_id (2)   44 unk_surface (" \xE2\x81\x87 ")   45 unk_piece   46 bos_piece ("<s>")   47 eos_piece ("</s>")
 //   NormalizerSpec  2 precompiled_charsmap (bytes)   3 add_dummy_prefix   4 remove_extra_whitespaces   5 escape_whitespaces (all true)
 // Absent fields keep the defaults above, the last occurrence of a scalar wins, a sub-message that occurs twice is merged, unknown
 // fields are skipped by their wire type, an enum value the proto does not declare is dropped (proto2).  The bytes are untrusted:
@@ -34,9 +34,13 @@ struct SpModel {
     bool byte_fallback = false, treat_whitespace_as_suffix = false;
     int32_t unk_id = 0, bos_id = 1, eos_id = 2;
     std::string unk_piece = "<unk>", bos_piece = "<s>", eos_piece = "</s>";
+    std::string unk_surface;        // what Decode writes for the unknown piece, if the field is present (has_unk_surface)
+    bool has_unk_surface = false;
     // normalizer_spec
     std::string precompiled_charsmap;
     bool add_dummy_prefix = true, remove_extra_whitespaces = true, escape_whitespaces = true;
+    // denormalizer_spec
+    std::string denormalizer_charsmap;
 };
 
 namespace sp_wire {
@@ -135,7 +139,10 @@ inline bool sp_model_parse(const uint8_t* data, size_t len, SpModel& m, std::str
                     else if (f == 41) m.bos_id = i;
                     else if (f == 42) m.eos_id = i;
                 } else if (w == 2) {
-                    if (f == 45) m.unk_piece = str_of(s);
+                    if (f == 44) {
+                        m.unk_surface = str_of(s);
+                        m.has_unk_surface = true;
+                    } else if (f == 45) m.unk_piece = str_of(s);
                     else if (f == 46) m.bos_piece = str_of(s);
                     else if (f == 47) m.eos_piece = str_of(s);
                 }
@@ -151,6 +158,12 @@ inline bool sp_model_parse(const uint8_t* data, size_t len, SpModel& m, std::str
                 return true;
             });
             where = "normalizer_spec";
+        } else if (field == 5) {
+            sub_ok = each_field(sub, [&](uint32_t f, int w, uint64_t, const Reader& s) {
+                if (f == 2 && w == 2) m.denormalizer_charsmap = str_of(s);
+                return true;
+            });
+            where = "denormalizer_spec";
         }
         return sub_ok;
     });

@@ -1064,6 +1064,86 @@ class SentencepieceTokenizer(_Op):
         return [idx[:2 * out.n].reshape(-1, 2), val[:out.n], shape[:2]]
 
 
+class SentencepieceDetokenizer(_Op):
+    """Reference: src/sentence_piece.cpp (evaluate :395-433).  Inputs: sp_model u8 (a serialized sentencepiece ModelProto, read at the
+    first evaluate), ids i32 [batch, seq].  Outputs: begins, ends i32 [batch], chars u8 -- per row SentencePieceProcessor::Decode over
+    the ids below the model's piece count.  Any model type decodes.  What is refused, and why: include/ovtk_amd.h,
+    ovtk_sp_detokenizer_run."""
+
+    _stream_mode = 0
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ovtk_sp_detokenizer_destroy(self._h)
+            self._h = None
+
+    def _ensure(self, model):
+        if self._h:
+            return
+        buf = np.frombuffer(_bytes_of(model), np.uint8)
+        self._chk(self._lib.ovtk_sp_detokenizer_create(buf.ctypes.data_as(C.c_void_p) if len(buf) else None, C.c_int64(len(buf)), self.device,
+                                                       C.byref(self._h)))
+
+    def bound(self, batch, seq_len):
+        """Bytes that suffice for any ids of this shape (ovtk_sp_detokenizer_bound); the handle must exist (after a first evaluate)."""
+        return int(self._lib.ovtk_sp_detokenizer_bound(self._h, C.c_int64(batch), C.c_int64(seq_len)))
+
+    def _prep(self, inputs):
+        if len(inputs) != 2:
+            raise L.OvtkError(L.E_ARG, f"{type(self).__name__} expects two inputs: sp model and token ids")   # :379, :462
+        self._ensure(inputs[0])
+        ids = inputs[1]
+        if len(ids.shape) != 2:
+            raise L.OvtkError(L.E_ARG, f"{type(self).__name__} expects 2D tensor as second input")   # :385, :468
+        m = _Mem(ids)
+        ids, pids = m.inp(ids, "i32")
+        return m, pids, int(ids.shape[0]), int(ids.shape[1])
+
+    def evaluate(self, inputs, chars_capacity=None):
+        m, pids, B, S = self._prep(inputs)
+        ob, pob = m.alloc(B, "i32")
+        oe, poe = m.alloc(B, "i32")
+        # a token gives far fewer bytes than the longest piece has: a first buffer of 8 bytes per id, and the size the library reports otherwise
+        cap = min(self.bound(B, S), 8 * B * S + 64) if chars_capacity is None else int(chars_capacity)
+        for attempt in range(2):
+            oc, poc = m.alloc(cap, "u8")
+            out = L.StringsOut(pob, poe, poc, cap, 0)
+            rc = self._lib.ovtk_sp_detokenizer_run(self._h, pids, C.c_int64(B), C.c_int64(S), self._stream_mode, C.byref(out), m.mem, m.stream)
+            if rc != L.E_CAPACITY or chars_capacity is not None or attempt:
+                break
+            cap = int(out.n_chars)
+        self._chk(rc)
+        return [ob[:B], oe[:B], oc[:out.n_chars]]
+
+    def enqueue(self, inputs, chars_capacity=None):
+        """evaluate() in two halves for CUDA tensors (ovtk_sp_detokenizer_enqueue / _finish): launches the passes on torch's current
+        stream and returns a ticket; `ticket()` waits for them and returns evaluate()'s outputs.  The buffer is chars_capacity bytes,
+        or bound() of them."""
+        m, pids, B, S = self._prep(inputs)
+        if not m.torch:
+            raise L.OvtkError(L.E_ARG, "enqueue() needs device-resident (torch CUDA) inputs")
+        cap = self.bound(B, S) if chars_capacity is None else int(chars_capacity)
+        ob, pob = m.alloc(B, "i32")
+        oe, poe = m.alloc(B, "i32")
+        oc, poc = m.alloc(cap, "u8")
+        out = L.StringsOut(pob, poe, poc, cap, 0)
+        pending = C.c_void_p()
+        self._chk(self._lib.ovtk_sp_detokenizer_enqueue(self._h, pids, C.c_int64(B), C.c_int64(S), self._stream_mode, C.byref(out), m.stream,
+                                                        C.byref(pending)))
+
+        def ticket(_keep=(m, inputs)):
+            self._chk(self._lib.ovtk_sp_detokenizer_finish(pending, C.byref(out)))
+            return [ob[:B], oe[:B], oc[:out.n_chars]]
+        return ticket
+
+
+class SentencepieceStreamDetokenizer(SentencepieceDetokenizer):
+    """Reference: src/sentence_piece.cpp (evaluate :478-523).  Same inputs and outputs; every piece is copied as it is (the space
+    symbol, control pieces and <unk> included), a piece of the shape <0xHH> becomes its byte."""
+
+    _stream_mode = 1
+
+
 class RaggedToSparse(_Op):
     """Reference: src/ragged_to_sparse.cpp (evaluate :27-47).  Inputs: begins, ends (i32).  Output: i32 [n, 2], (row, position) of
     every element of every row."""

@@ -320,6 +320,19 @@ class SentencepieceModelStep(Step):
         return "dense", [ids, mask]
 
 
+class SentencepieceDetokenizeStep(Step):
+    """src/sentence_piece.cpp:395-433 (stream=False: SentencePieceProcessor::Decode) or :478-523 (stream=True: the pieces as they
+    are): ids [B, S] -> one string per row.  `model`: the serialized sentencepiece model.  fuse() leaves the step as it is."""
+
+    def __init__(self, model, stream=False, lib=None):
+        self.model = np.frombuffer(bytes(model), np.uint8)
+        self.op = (K.SentencepieceStreamDetokenizer if stream else K.SentencepieceDetokenizer)(lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "tokens"
+        return "text", self.op.evaluate([self.model, vals[0]])
+
+
 class TruncationStep(Step):
     """src/truncate.cpp:37-150, one input."""
 

@@ -14,6 +14,13 @@ they make, and whether a prefix of the result equals the oracle's.  The kernels'
 `rocprofv3 --kernel-trace --stats` (profiles/README.md); VERDICT r04 weak 6 asked for both.
 
     python tools/ops_timing.py [--rows 65536] [--bytes 512] [--reps 10] [--check-rows 256] [--only-sentencepiece]
+
+--only-sp-detok times SentencepieceDetokenizer and SentencepieceStreamDetokenizer instead, on one 16 384 x 2 048 id matrix (the
+config-2 batch's first rows encoded with spm_unigram_bytes, padded with an id outside the vocabulary), and beside them, in the same
+run, ovtk_detokenize_run with byte_fallback = 1 over the same piece list as a vocabulary -- a different algorithm with different
+bytes, and the only yardstick there is.
+
+    python tools/ops_timing.py --only-sp-detok [--detok-rows 16384] [--detok-seq 2048]
 """
 from __future__ import annotations
 
@@ -79,6 +86,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--check-rows", type=int, default=256)
     ap.add_argument("--only-sentencepiece", action="store_true", help="the SentencepieceTokenizer rows and nothing else")
+    ap.add_argument("--only-sp-detok", action="store_true", help="the two sentencepiece detokenizers beside ovtk_detokenize_run and nothing else")
+    ap.add_argument("--detok-rows", type=int, default=16384)
+    ap.add_argument("--detok-seq", type=int, default=2048)
     ap.add_argument("--emu", action="store_true", help="the SIMT-emulator build on host arrays (a smoke test of this script; the times mean nothing)")
     args = ap.parse_args()
     from openvino_tokenizers_amd import _lib as L
@@ -99,6 +109,8 @@ def main():
         dev = torch.device("cuda", 0)
         sync = torch.cuda.synchronize
     tok = BpeTok.load("gpt2")
+    if args.only_sp_detok:
+        args.rows = args.detok_rows
     n = args.rows
     b, e, c = TextModel(1234, "zipf").batch(n, args.bytes, seed=1000)
     rng = np.random.default_rng(1)
@@ -140,6 +152,48 @@ def main():
         return out
 
     n_c = len(c)
+    if args.only_sp_detok:
+        # ---- SentencepieceDetokenizer / SentencepieceStreamDetokenizer (src/sentence_piece.cpp:395-433, :478-523)
+        from openvino_tokenizers_amd.ops import (FusedDetokenizer, SentencepieceDetokenizer, SentencepieceStreamDetokenizer, SentencepieceTokenizer,
+                                                 VocabDecoder)
+        model = np.frombuffer((Path(__file__).resolve().parent.parent / "tests" / "golden" / "spm_unigram_bytes.model").read_bytes(), np.uint8)
+        pieces = sp_model_tables(model)[0]
+        V, S = len(pieces), args.detok_seq
+        idx, val, shape = SentencepieceTokenizer(lib=lib).evaluate([model] + d[2:5])
+        idx, val = to_np(idx), to_np(val)
+        keep = idx[:, 1] < S
+        ids_host = np.full((n, S), V, np.int32)
+        ids_host[idx[keep, 0], idx[keep, 1]] = val[keep]
+        ids = ids_host if args.emu else torch.as_tensor(ids_host, device=dev)
+        n_ids = int(keep.sum())
+        want = None
+        try:
+            import sentencepiece as spm
+            sp = spm.SentencePieceProcessor(model_proto=bytes(model))
+            want = [sp.decode([int(x) for x in row if x < V]).encode() for row in ids_host[:k]]
+        except ImportError:
+            pass
+
+        def rows_equal(out):
+            if want is None:
+                return None
+            ob, oe, oc = [to_np(x) for x in out]
+            return [bytes(oc[ob[r]:oe[r]]) for r in range(k)] == want
+        dec_op, str_op = SentencepieceDetokenizer(lib=lib), SentencepieceStreamDetokenizer(lib=lib)
+        old = FusedDetokenizer(VocabDecoder(lib=lib), byte_fallback=True)
+        vocab = list(pack_strings(pieces))
+        n_out = len(dec_op.evaluate([model, ids])[2])
+        cap = n_out + 64   # (the buffers are sized once: the stream op's text is longer where a space symbol stays three bytes)
+        cap_raw = len(str_op.evaluate([model, ids])[2])
+        n_old = len(old.evaluate([ids] + vocab)[2])
+        for trial in range(3):
+            timed(f"SentencepieceDetokenizer(spm_unigram_bytes), round {trial}", lambda: dec_op.evaluate([model, ids], chars_capacity=cap),
+                  4 * n * S + n_out + 8 * n, rows_equal, f"{n} x {S} ids, {n_ids} in the vocabulary, {n_out} bytes out: first -> count -> scan -> write")
+            timed(f"SentencepieceStreamDetokenizer(spm_unigram_bytes), round {trial}", lambda: str_op.evaluate([model, ids], chars_capacity=cap_raw),
+                  4 * n * S + cap_raw + 8 * n, None, f"the same ids, {cap_raw} bytes out: count -> scan -> write over the raw pieces")
+            timed(f"ovtk_detokenize_run(byte_fallback=1, the same pieces as a vocabulary), round {trial}", lambda: old.evaluate([ids] + vocab),
+                  4 * n * S + n_old + 8 * n, None, f"{n_old} bytes out; VocabDecoder -> ByteFallback -> FuzeRagged in one call: other bytes (no spaces for the space symbol, control pieces kept)")
+        return
     # ---- SentencepieceTokenizer (src/sentence_piece.cpp:188-350), the fixture unigram model with the nmt_nfkc charsmap: one call; beside
     # it the two calls it replaces, CharsMapNormalization then UnigramTokenizer over whole rows with the model's own tables (three
     # rounds of each, alternating: the spread of the pair is the yardstick for the one call).  The check: the one call's ids are the
