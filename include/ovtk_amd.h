@@ -153,7 +153,12 @@ void ovtk_special_tokens_split_destroy(ovtk_special_tokens_split* h);
  * piece store, below) is sized by this library already.  So by default (0) the first level learns up to
  * max(cache_capacity, the store's capacity) pieces -- what the store would hold for every later call to fetch from
  * merge_kernel is found by the lookup kernel instead --; < 0: exactly cache_capacity pieces, the reference's count;
- * > 0: that many.  (Round 5: ABI 1002.  Until then the count was cache_capacity and an entry held 3 ids.) */
+ * > 0: that many.  (Round 5: ABI 1002.  Until then the count was cache_capacity and an entry held 3 ids.)
+ * Limit of the merge table (a deviation from the reference, which accepts any merges): a merge is found by two loads whose addresses
+ * both come from one 32-bit hash of its (left id, right id) pair, so at most TWO merges may share that hash.  ovtk_bpe_create returns
+ * OVTK_E_UNSUPPORTED for a table with three or more such merges -- ovtk_last_error() names them by their index in `merges` -- and for
+ * one that cannot be placed in 2^26 slots.  Expected once in thousands of Llama-3-sized tables, likely only near 2^22 merges; no
+ * triple exists among fewer than 83 969 token ids ("Limits of the merge table"). */
 typedef struct ovtk_bpe_params {
     ovtk_strings vocab;
     ovtk_strings merges;       /* text lines or left halves */

@@ -118,9 +118,9 @@ bool TrieBucketsHost::build(const TrieHost& t) {
 // ------------------------------------------------------------------------------- BPE
 namespace {
 // Cuckoo insertion by random walk (deterministic xorshift): `choices(item, idx)` fills the candidate slot
-// indices of an item, `empty(slot)` tells a free slot.  Returns false when the walk does not terminate.
+// indices of an item, `empty(slot)` tells a free slot.  Returns false when the walk does not terminate; `kicks` counts the evictions.
 template <class Slot, int N, class Choices, class Empty>
-bool cuckoo_insert(std::vector<Slot>& slots, Slot item, Choices&& choices, Empty&& empty, uint64_t& rng) {
+bool cuckoo_insert(std::vector<Slot>& slots, Slot item, Choices&& choices, Empty&& empty, uint64_t& rng, uint32_t& kicks) {
     for (int kick = 0; kick < 2000; ++kick) {
         uint32_t idx[N];
         choices(item, idx);
@@ -133,6 +133,7 @@ bool cuckoo_insert(std::vector<Slot>& slots, Slot item, Choices&& choices, Empty
         rng ^= rng >> 7;
         rng ^= rng << 17;
         std::swap(item, slots[idx[rng % N]]);
+        ++kicks;
     }
     return false;
 }
@@ -216,11 +217,39 @@ int build_bpe(const StringsView& vocab, const StringsView& ml, const StringsView
     }
     out.suffix = end_suffix;
 
+    // merge_h1 and merge_h2 are both functions of merge_mix(key) alone, so merges whose keys share those 32 bits share BOTH candidate slots at
+    // every table size: two of them fill the two slots, a third has no place whatever the size.  (The reference's std::unordered_map takes any
+    // merge table; see DESIGN.md "Limits of the merge table" for how often a real one gets here.)
+    {
+        std::vector<std::pair<uint32_t, uint32_t>> by_mix;   // (merge_mix, rank)
+        by_mix.reserve(rank_of.size());
+        for (const auto& kv : rank_of) by_mix.emplace_back(merge_mix(kv.first), kv.second);
+        std::sort(by_mix.begin(), by_mix.end());
+        for (size_t i = 0, j; i < by_mix.size(); i = j) {
+            for (j = i + 1; j < by_mix.size() && by_mix[j].first == by_mix[i].first; ++j) {}
+            if (j - i <= 2) continue;
+            err = "BPETokenizer: merges";
+            for (size_t k = i; k < j && k < i + 8; ++k) err += (k == i ? " " : ", ") + std::to_string(by_mix[k].second);
+            if (j - i > 8) err += ", ...";
+            err += " have (left id, right id) pairs with one and the same 32-bit hash; the device merge table has two slots per hash value, so "
+                   "more than two such merges are not supported";
+            return OVTK_E_UNSUPPORTED;
+        }
+    }
     // Cuckoo table: 2 hash functions x 1 slot (load < 0.5 of the slots; grown until every pair is placed).
-    for (uint32_t buckets = std::max<uint32_t>(4, pow2_at_least(uint64_t(rank_of.size()) * 2 + 1));; buckets *= 2) {
+    // The growth ends at kMaxMergeBuckets = 2^26 slots (1 GiB of 16-byte slots).  Why there: the largest table the limits above allow STARTS at
+    // 2^23 slots (2^22 merges), so the cap leaves every table at least three doublings; at a sixteenth of the load a two-choice cuckoo table
+    // takes, what still fails is not crowding but keys that cannot be told apart -- and after the check above those are distinct mixes, which
+    // the top bits of two odd multiplies separate as the table grows (h1, h2 use up to 26 of the 32 bits here).  What is left for the cap are
+    // crafted keys (two merges with merge_mix == 0 have h1 == h2 == 0 at every size); it only has to exist, and it keeps `buckets`, a
+    // uint32_t, from doubling to 0 and bucket_shift from reaching 32 - 32.
+    constexpr uint32_t kMaxMergeBuckets = 1u << 26;
+    bool placed = false;
+    for (uint32_t buckets = std::max<uint32_t>(4, pow2_at_least(uint64_t(rank_of.size()) * 2 + 1)); buckets <= kMaxMergeBuckets; buckets *= 2) {
         out.bucket_shift = 32 - log2u(buckets);
         std::vector<MergeSlot> flat(size_t(buckets), MergeSlot{kEmptySlot, 0});
         uint64_t rng = 0x2545F4914F6CDD1Dull;
+        uint32_t kicks = 0;
         bool ok = true;
         const uint32_t shift = out.bucket_shift;
         for (const auto& kv : rank_of) {
@@ -232,13 +261,19 @@ int build_bpe(const StringsView& vocab, const StringsView& ml, const StringsView
                     idx[0] = merge_h1(key, shift);
                     idx[1] = merge_h2(key, shift);
                 },
-                [](const MergeSlot& m) { return m.kr == kEmptySlot; }, rng);
+                [](const MergeSlot& m) { return m.kr == kEmptySlot; }, rng, kicks);
             if (!ok) break;
         }
         if (!ok) continue;
         out.merges.resize(buckets);
         std::memcpy(out.merges.data(), flat.data(), flat.size() * sizeof(MergeSlot));
+        out.merge_kicks = kicks;
+        placed = true;
         break;
+    }
+    if (!placed) {
+        err = "BPETokenizer: the merges do not fit a device merge table of 2^26 slots (their (left id, right id) pairs hash to the same slots at every size)";
+        return OVTK_E_UNSUPPORTED;
     }
     return OVTK_OK;
 }

@@ -213,8 +213,10 @@ __host__ __device__ inline uint64_t hash_u64(uint64_t k) { return k * 0x9E3779B9
 __host__ __device__ inline uint64_t merge_key(uint32_t l, uint32_t r) { return (uint64_t(l) << kMaxVocabBits) | r; }
 // Cuckoo hash functions: the top log2(buckets) bits of odd-constant multiplies (shift = 64 - log2(buckets) < 64).
 // (32-bit arithmetic: a 64-bit multiply costs ~5 vector instructions at a quarter of the rate; key < 2^42)
+// (the sum under its own name: it is linear in the two key halves, which is what tests/emu/table_collisions.cpp searches equal mixes with)
+__host__ __device__ inline uint32_t merge_mix_sum(uint64_t key) { return uint32_t(key) * 0x9E3779B1u + uint32_t(key >> 32) * 0x85EBCA77u; }
 __host__ __device__ inline uint32_t merge_mix(uint64_t key) {
-    uint32_t h = uint32_t(key) * 0x9E3779B1u + uint32_t(key >> 32) * 0x85EBCA77u;
+    const uint32_t h = merge_mix_sum(key);
     return h ^ (h >> 15);
 }
 __host__ __device__ inline uint32_t merge_h1(uint64_t key, uint32_t shift) { return (merge_mix(key) * 0x2C1B3C6Du) >> shift; }
@@ -292,6 +294,7 @@ struct BpeHost {
     TrieHost trie;
     std::vector<MergeBucket> merges;
     uint32_t bucket_shift = 30;
+    uint32_t merge_kicks = 0;   // evictions the cuckoo build of `merges` needed (host-side bookkeeping: tests/emu/table_collisions.cpp reports it)
     std::vector<int32_t> new_id;
     std::vector<int32_t> byte_fallback_id;
     int32_t unk_id = -1;
