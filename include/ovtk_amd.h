@@ -696,6 +696,32 @@ int ovtk_sp_detokenizer_enqueue(ovtk_sp_detokenizer* h, const int32_t* ids, int6
                                 void* stream, ovtk_pending** pending);
 int ovtk_sp_detokenizer_finish(ovtk_pending* pending, ovtk_strings_out* out);
 
+/* ---------------------------------------------------------------- StringToHashBucket / EqualStr / RaggedToRagged
+ * The three ops that only the reference's TensorFlow front end creates (src/tensorflow_translators.cpp); stateless.
+ * ovtk_string_to_hash_bucket replaces StringToHashBucket::evaluate, src/string_to_hash_bucket.cpp:204-220: out[i] = FarmHash
+ * Fingerprint64 of string i (hash64, :128-182) modulo num_buckets, unsigned 64-bit, as i64; out: [in->n].  num_buckets <= 0 is
+ * OVTK_E_ARG (:199); begins[i] > ends[i] (:215) or an offset outside the chars tensor is OVTK_E_RANGE.
+ * ovtk_equal_str replaces EqualStr::evaluate, src/equal_str.cpp:29-61: *n_out = (a->n == 0 || b->n == 0) ? 0 : max(a->n, b->n);
+ * out[i] = 1 where string (i < a->n ? i : 0) of a has the bytes of string (i < b->n ? i : 0) of b, else 0 -- the reference's rule,
+ * not NumPy's: sizes 3 and 2 are not refused, element 2 compares with b's string 0.  a and b may be the same buffers.  capacity <
+ * *n_out is OVTK_E_CAPACITY (*n_out is set, nothing written); an offset outside its chars tensor is OVTK_E_RANGE.
+ * ovtk_ragged_to_ragged replaces RaggedToRagged::evaluate, src/ragged_to_ragged.cpp:43-98: non-decreasing row ids [n_rowids] ->
+ * out_begins / out_ends [batch_size] (batch_size: first_dim_size[0], read by the caller).  A row that occurs is [first index, one
+ * past its last index); a row without ids is [i, i), i = the start of the next run (0 in front of the first id, n_rowids behind the
+ * last, 0 everywhere when n_rowids == 0).  batch_size < 0 is OVTK_E_ARG.
+ * Choices of this library where the reference asserts, stops early or depends on the order of its writes:
+ *   - a negative row id (the reference asserts, :61): OVTK_E_RANGE;
+ *   - ids >= batch_size from index j on (the reference leaves its loop at j, :62-64): with s the start of the last run in range,
+ *     the rows behind that run's row are [s, s) -- the reference's value, s and not j -- and the run's own row, which the reference
+ *     leaves unwritten, is [s, j); when the very first id is out of range every row is [0, 0);
+ *   - an id below the one before it (TensorFlow's value_rowids are sorted; the reference overwrites in input order): OVTK_E_ARG,
+ *     nothing is promised about the outputs. */
+int ovtk_string_to_hash_bucket(const ovtk_strings* in, int64_t num_buckets, int64_t* out, int mem, int device, void* stream);
+int ovtk_equal_str(const ovtk_strings* a, const ovtk_strings* b, int32_t* out, int64_t capacity, int64_t* n_out, int mem, int device,
+                   void* stream);
+int ovtk_ragged_to_ragged(const int32_t* rowids, int64_t n_rowids, int32_t batch_size, int32_t* out_begins, int32_t* out_ends, int mem,
+                          int device, void* stream);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py)
  * With profiling on, every kernel launch of the library is bracketed by hipEvents on the stream it is
  * launched on; times are accumulated per kernel name after the call's own synchronisation. */

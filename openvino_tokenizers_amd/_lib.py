@@ -134,6 +134,7 @@ EXPORTS = [
     "ovtk_sentencepiece_create", "ovtk_sentencepiece_run", "ovtk_sentencepiece_bound", "ovtk_sentencepiece_destroy", "ovtk_ragged_to_sparse",
     "ovtk_sp_detokenizer_create", "ovtk_sp_detokenizer_run", "ovtk_sp_detokenizer_bound", "ovtk_sp_detokenizer_destroy",
     "ovtk_sp_detokenizer_enqueue", "ovtk_sp_detokenizer_finish",
+    "ovtk_string_to_hash_bucket", "ovtk_equal_str", "ovtk_ragged_to_ragged",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -205,6 +206,9 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_regex_normalization_bound.restype = C.c_int64
     lib.ovtk_regex_normalization_destroy.argtypes = [C.c_void_p]
     lib.ovtk_regex_normalization_destroy.restype = None
+    lib.ovtk_string_to_hash_bucket.argtypes = [C.POINTER(Strings), C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_equal_str.argtypes = [C.POINTER(Strings), C.POINTER(Strings), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_ragged_to_ragged.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _cache[key] = lib
     return lib
 

@@ -57,6 +57,7 @@ constexpr uint32_t kFlagRange = 32u;            // an input offset left its buff
 constexpr uint32_t kFlagExactOverflow = 64u;    // exact-path piece list too small
 constexpr uint32_t kFlagDidNotRun = 0x80000000u;  // host side only: what the pinned status block holds until compact_kernel has written it
 constexpr uint32_t kFlagTailPending = 128u;     // merge_kernel's folded tail left the exact pieces / row scan to separate launches
+constexpr uint32_t kFlagUnsorted = 256u;        // RaggedToRagged: a row id below the one before it
 
 __device__ __forceinline__ int lane_id() { return int(threadIdx.x) & (kWave - 1); }
 __device__ __forceinline__ int wave_in_block() { return int(threadIdx.x) >> 6; }

@@ -1163,6 +1163,69 @@ class RaggedToSparse(_Op):
         return [out[:2 * n.value].reshape(-1, 2)]
 
 
+class StringToHashBucket(_Op):
+    """Reference: src/string_to_hash_bucket.cpp (validate :190-202, evaluate :204-220).  Inputs: begins, ends, chars.  Output: i64 with
+    the shape of begins, FarmHash Fingerprint64 of every string modulo num_buckets (TensorFlow's StringToHashBucketFast)."""
+
+    def __init__(self, num_buckets, device=0, lib=None):
+        super().__init__(device, lib)
+        self.num_buckets = int(num_buckets)
+
+    def evaluate(self, inputs):
+        if len(inputs) != 3:
+            raise L.OvtkError(L.E_ARG, f"StringToHashBucket takes begins, ends and chars, got {len(inputs)} inputs")   # :191
+        m = _Mem(inputs[2])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        c, pc = m.inp(inputs[2], "u8")
+        shape = tuple(b.shape)
+        n = int(np.prod(shape, dtype=np.int64))
+        out, pout = m.alloc(n, "i64")
+        s = L.Strings(pb, pe, pc, n, len(c))
+        self._chk(self._lib.ovtk_string_to_hash_bucket(C.byref(s), C.c_int64(self.num_buckets), pout, m.mem, self.device, m.stream))
+        return [out[:n].reshape(shape)]
+
+
+class EqualStr(_Op):
+    """Reference: src/equal_str.cpp (evaluate :29-61).  Inputs: begins, ends, chars of the first operand, then of the second.
+    Output: i32 [n], n = 0 if either operand is empty else the larger count; element i compares string (i if i < n1 else 0) with
+    string (i if i < n2 else 0) -- the reference's broadcasting, not NumPy's."""
+
+    def evaluate(self, inputs, capacity=None):
+        if len(inputs) != 6:
+            raise L.OvtkError(L.E_ARG, f"EqualStr takes two string tensors (6 inputs), got {len(inputs)}")   # :14
+        m = _Mem(inputs[2])
+        ops = []
+        for j in (0, 3):
+            b, pb = m.inp(inputs[j], "i32")
+            e, pe = m.inp(inputs[j + 1], "i32")
+            c, pc = m.inp(inputs[j + 2], "u8")
+            ops.append(L.Strings(pb, pe, pc, b.numel() if m.torch else b.size, len(c)))
+        n1, n2 = ops[0].n, ops[1].n
+        cap = (0 if n1 == 0 or n2 == 0 else max(n1, n2)) if capacity is None else int(capacity)
+        out, pout = m.alloc(cap, "i32")
+        n = C.c_int64(0)
+        self._chk(self._lib.ovtk_equal_str(C.byref(ops[0]), C.byref(ops[1]), pout, C.c_int64(cap), C.byref(n), m.mem, self.device, m.stream))
+        return [out[:n.value]]
+
+
+class RaggedToRagged(_Op):
+    """Reference: src/ragged_to_ragged.cpp (evaluate :43-98).  Inputs: rowids (i32, non-decreasing), first_dim_size (i32, one element,
+    read on the host).  Outputs: begins, ends [first_dim_size[0]].  The edges the reference leaves open: include/ovtk_amd.h."""
+
+    def evaluate(self, inputs):
+        if len(inputs) != 2:
+            raise L.OvtkError(L.E_ARG, f"RaggedToRagged takes rowids and first_dim_size, got {len(inputs)} inputs")   # :14
+        batch = int(np.asarray(_host(inputs[1], np.int32)).reshape(-1)[0])
+        m = _Mem(inputs[0])
+        ids, pids = m.inp(inputs[0], "i32")
+        rows = max(batch, 0)
+        ob, pob = m.alloc(rows, "i32")
+        oe, poe = m.alloc(rows, "i32")
+        self._chk(self._lib.ovtk_ragged_to_ragged(pids, C.c_int64(len(ids)), C.c_int32(batch), pob, poe, m.mem, self.device, m.stream))
+        return [ob[:rows], oe[:rows]]
+
+
 class NormalizeUnicode(CharsMapNormalization):
     """Reference: src/normalize_unicode.cpp (evaluate :32-62): the charsmap of `normalization_form` (NFC, NFD, NFKC, NFKD) with all three
     flags off.  Strings (3) [+ skips] -> strings (3) [+ skips].  `charsmap=`: the form's precompiled table (see CharsMapNormalization)."""

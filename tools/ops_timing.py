@@ -21,6 +21,12 @@ run, ovtk_detokenize_run with byte_fallback = 1 over the same piece list as a vo
 bytes, and the only yardstick there is.
 
     python tools/ops_timing.py --only-sp-detok [--detok-rows 16384] [--detok-seq 2048]
+
+--only-tf-ops times the three ops of the TensorFlow front end and nothing else (the full run ends with them): StringToHashBucket over
+whole rows and over the batch split on whitespace (a division and a mask as the modulo), EqualStr of the rows against one constant and
+against themselves, RaggedToRagged on the row id of every word, and UTF8Validate on the same batch in the same run -- it also reads
+every byte of the batch once: the yardstick for the whole-row hash.  The checks are tests/test_tf_string_ops.py's restatements on the
+first rows.
 """
 from __future__ import annotations
 
@@ -87,6 +93,7 @@ def main():
     ap.add_argument("--check-rows", type=int, default=256)
     ap.add_argument("--only-sentencepiece", action="store_true", help="the SentencepieceTokenizer rows and nothing else")
     ap.add_argument("--only-sp-detok", action="store_true", help="the two sentencepiece detokenizers beside ovtk_detokenize_run and nothing else")
+    ap.add_argument("--only-tf-ops", action="store_true", help="StringToHashBucket, EqualStr, RaggedToRagged beside UTF8Validate and nothing else")
     ap.add_argument("--detok-rows", type=int, default=16384)
     ap.add_argument("--detok-seq", type=int, default=2048)
     ap.add_argument("--emu", action="store_true", help="the SIMT-emulator build on host arrays (a smoke test of this script; the times mean nothing)")
@@ -152,6 +159,50 @@ def main():
         return out
 
     n_c = len(c)
+
+    def tf_ops():
+        # ---- StringToHashBucket (src/string_to_hash_bucket.cpp:204-220), EqualStr (src/equal_str.cpp:29-61), RaggedToRagged
+        # (src/ragged_to_ragged.cpp:43-98); UTF8Validate beside them: the other op that reads every byte of the batch once
+        from openvino_tokenizers_amd.ops import EqualStr, RaggedToRagged, StringToHashBucket
+        from tests.test_tf_string_ops import equal_ref, fingerprint64, ragged_ref
+        uv = UTF8Validate(replace_mode=False, lib=lib)
+        timed("UTF8Validate(replace_mode=False), the yardstick", lambda: uv.evaluate(d[2:5]), 2 * n_c + 16 * n, None,
+              "reads every byte once and writes it once; count -> scan -> write, a wave per string")
+        rows = [bytes(c[int(b[i]):int(e[i])]) for i in range(k)]
+        row_hashes = [fingerprint64(r) for r in rows]
+        for nb, how in ((1000, "64-bit division"), (1 << 20, "mask")):
+            op = StringToHashBucket(nb, lib=lib)
+            timed(f"StringToHashBucket(num_buckets={nb}), whole rows", lambda op=op: op.evaluate(d[2:5]), n_c + 16 * n,
+                  lambda out, nb=nb: same([np.array([h % nb for h in row_hashes], np.int64)], [to_np(out[0])[:k]]),
+                  f"a lane per row streams its own ~{args.bytes} bytes, 64 per round of the loop; the modulo is a {how}")
+        ws_out = RegexSplit("remove", lib=lib).evaluate(d + [np.frombuffer(rb"\s+", np.uint8)])
+        n_words = len(ws_out[2])
+        wb, we = to_np(ws_out[2]), to_np(ws_out[3])
+        kw = min(4096, n_words)
+        word_hashes = [fingerprint64(bytes(c[int(wb[i]):int(we[i])])) for i in range(kw)]
+        for nb, how in ((1000, "64-bit division"), (1 << 20, "mask")):
+            op = StringToHashBucket(nb, lib=lib)
+            timed(f"StringToHashBucket(num_buckets={nb}), the batch split on whitespace", lambda op=op: op.evaluate(list(ws_out[2:5])),
+                  n_c + 16 * n_words, lambda out, nb=nb: same([np.array([h % nb for h in word_hashes], np.int64)], [to_np(out[0])[:kw]]),
+                  f"{n_words} strings, a lane each: the 0-16 byte branches; the modulo is a {how}")
+        eq = EqualStr(lib=lib)
+        const = [np.array([3], np.int32), np.array([3 + len(rows[0])], np.int32), np.frombuffer(b"xyz" + rows[0], np.uint8)]
+        const_d = const if args.emu else [torch.as_tensor(x, device=dev) for x in const]
+        timed("EqualStr(rows, one constant)", lambda: eq.evaluate(d[2:5] + const_d), 12 * n, lambda out: same([equal_ref(rows, [rows[0]])], [to_np(out[0])[:k]]),
+              "the constant is row 0: bytes are compared only where the lengths agree (offsets in, i32 out)")
+        timed("EqualStr(rows, rows)", lambda: eq.evaluate(d[2:5] + d[2:5]), 2 * n_c + 20 * n, lambda out: same([equal_ref(rows, rows)], [to_np(out[0])[:k]]),
+              "both operands the same tensors: every byte is fetched twice, eight at a time, a lane per row")
+        counts = to_np(ws_out[1]).astype(np.int64) - to_np(ws_out[0])
+        rowids = np.repeat(np.arange(n, dtype=np.int32), counts)
+        rowids_d = rowids if args.emu else torch.as_tensor(rowids, device=dev)
+        ref_r = ragged_ref(rowids, k)   # (stops at the first id >= k: rows 0 .. k - 2 are the whole batch's)
+        r2r = RaggedToRagged(lib=lib)
+        timed("RaggedToRagged(row id of every word)", lambda: r2r.evaluate([rowids_d, np.array([n], np.int32)]), 4 * len(rowids) + 8 * n,
+              lambda out: same([ref_r[0][:k - 1], ref_r[1][:k - 1]], [to_np(out[0])[:k - 1], to_np(out[1])[:k - 1]]),
+              f"{len(rowids)} ids, batch_size {n}: a lane per id, run starts write")
+    if args.only_tf_ops:
+        tf_ops()
+        return
     if args.only_sp_detok:
         # ---- SentencepieceDetokenizer / SentencepieceStreamDetokenizer (src/sentence_piece.cpp:395-433, :478-523)
         from openvino_tokenizers_amd.ops import (FusedDetokenizer, SentencepieceDetokenizer, SentencepieceStreamDetokenizer, SentencepieceTokenizer,
@@ -386,6 +437,7 @@ def main():
           lambda: tail.evaluate([bos_d, (ib, ie, ids), bos_d], seg_ids, truncated=(1,), pad_value=50256, target_dim=T),
           4 * kept + 9 * n * T + 8 * n, lambda out: same([ref_d[0]], [to_np(out[0])[:k]]),
           "one call, one kernel behind the width measurement; input_ids + attention_mask + token_type_ids")
+    tf_ops()
     print(json.dumps({"batch": {"rows": n, "text_bytes": n_c, "ids": n_t, "ids_kept_by_truncate": kept}}))
 
 
