@@ -722,6 +722,68 @@ int ovtk_equal_str(const ovtk_strings* a, const ovtk_strings* b, int32_t* out, i
 int ovtk_ragged_to_ragged(const int32_t* rowids, int64_t n_rowids, int32_t batch_size, int32_t* out_begins, int32_t* out_ends, int mem,
                           int device, void* stream);
 
+/* ---------------------------------------------------------------- BytesToChars / CharsToBytes / ContribStringSplit / ContribStringJoin
+ * Stateless; device kernels only (no device: OVTK_E_HIP).  Variable-length outputs follow one protocol: a buffer that is too small
+ * is OVTK_E_CAPACITY with the sizes the call needs reported (n_chars, n_values) and nothing written; text (or values) that would
+ * reach 2^31 is OVTK_E_UNSUPPORTED: split the call.
+ * The byte <-> character map is GPT-2's bytes_to_unicode: bytes 33..126, 161..172 and 174..255 map to the code point of the same
+ * value, the other 68 bytes, in ascending order, to U+0100..U+0143; a character is written as its UTF-8 (one byte for 33..126, two
+ * otherwise).
+ *
+ * ovtk_bytes_to_chars replaces BytesToChars::evaluate, src/bytes_to_chars.cpp:284-339.  Rows are visited in order, a row's elements
+ * in order; each element's text is written back to back from 0: out->begins / out->ends [in->strings.n], out->chars.  An element with
+ * skips[i] != 0 (skips: u8[in->strings.n] or NULL, the 6-input form) is copied unchanged, every other byte goes through the map.
+ * ragged_begins / ragged_ends and skips pass through: they are the caller's (the reference's outputs[0] = inputs[0]).  2 bytes per
+ * input byte of the covered elements suffice (the reference sizes 2 * n_chars, :299).  Where the reference is undefined:
+ *   - an element no row covers gets begins = ends = 0 (the reference leaves both uninitialised);
+ *   - a row that begins before the row in front of it ended is OVTK_E_UNSUPPORTED (the reference would write that text twice and
+ *     keep the later offsets); rows in order may leave gaps, and the elements' own offsets need be neither ordered nor gap-free;
+ *   - a negative offset, an offset outside its tensor or end < begin -- of a row, or of an element a row covers -- is OVTK_E_RANGE.
+ *
+ * ovtk_chars_to_bytes replaces CharsToBytes::evaluate, src/chars_to_bytes.cpp:31-68: one string per row, out->begins / out->ends
+ * [in->n_rows] back to back from 0 -- the row's elements fused and mapped back: a byte below 128 is copied, a lead byte 194..197
+ * with its continuation byte 128..191 becomes the byte whose image that pair is.  The input's size in bytes suffices.  Offsets and
+ * row order: the rules above.  Input outside the 256 images is undefined in the reference (it reads an uninitialised or
+ * out-of-range table slot, or the byte past the element's end); here the whole call is OVTK_E_RANGE and nothing is promised about
+ * the outputs.  The rule is local, a lane per byte decides it: a byte 194..197 must be followed inside its element by a byte
+ * 128..191 and the pair must be an image; a byte 128..191 must be preceded inside its element by a byte 194..197; a byte 192, 193
+ * or >= 198 is an error.  This equals the reference's left-to-right walk on every well-defined input: lead bytes and continuation
+ * bytes are disjoint sets, so where every byte >= 128 belongs to an image pair the walk's pairing is the only one there is, and a
+ * byte's role follows from the byte itself and its neighbour.
+ *
+ * ovtk_contrib_string_split replaces ContribStringSplit::evaluate, src/contrib_string_ops.cpp:225-343.  in: the elements of a
+ * tensor of `shape` (i64[rank], HOST memory; rank 0..8, more is OVTK_E_UNSUPPORTED; the shape's product must be in->n); delim:
+ * delim_len bytes in HOST memory.  Tokens are what std::string_view::find yields from the left, without overlap: an element
+ * without the delimiter is one token (the empty element too: one empty token); an empty delimiter splits into single bytes (an empty
+ * element then gives no token); with skip_empty empty tokens give no value but still count in the positions and in dense_shape.
+ * Outputs: indices i64 [n_values][rank + 1] (the element's coordinates, then the token's position before skipping), the values'
+ * begins / ends [n_values] back to back from 0 and chars, dense_shape i64[rank + 1] (HOST memory: the input shape, then the largest
+ * token count of any element, counted before skipping).  n + (sum of the elements' lengths) values and that sum of bytes suffice.
+ * end < begin (the reference asserts, :265) or an offset outside the chars tensor is OVTK_E_RANGE. */
+typedef struct ovtk_string_split_out {
+    int64_t* indices;        /* [values_capacity][rank + 1] */
+    int32_t* begins;         /* [values_capacity] */
+    int32_t* ends;
+    uint8_t* chars;          /* [chars_capacity] */
+    int64_t* dense_shape;    /* [rank + 1], HOST memory */
+    int64_t values_capacity;
+    int64_t chars_capacity;
+    int64_t n_values;        /* out */
+    int64_t n_chars;         /* out */
+} ovtk_string_split_out;
+/* ovtk_contrib_string_join replaces ContribStringJoin::evaluate, src/contrib_string_ops.cpp:62-199.  Output o is the elements along
+ * `axis` (negative: from the back) at o's coordinates, in order, with sep (sep_len bytes, HOST memory) between them; out->begins /
+ * out->ends [*n_out], *n_out = the product of the other dimensions, back to back from 0.  axis out of range for rank >= 1 is
+ * OVTK_E_ARG (:91).  Rank 0 and any one-element input give that one string (the reference's early branch, :100-120); an axis of
+ * size 0 gives empty strings; a shape with a zero elsewhere gives no output.  end < begin or an offset outside the chars tensor is
+ * OVTK_E_RANGE (the reference reads whatever is there). */
+int ovtk_bytes_to_chars(const ovtk_ragged_strings* in, const uint8_t* skips, ovtk_strings_out* out, int mem, int device, void* stream);
+int ovtk_chars_to_bytes(const ovtk_ragged_strings* in, ovtk_strings_out* out, int mem, int device, void* stream);
+int ovtk_contrib_string_split(const ovtk_strings* in, const int64_t* shape, int rank, const uint8_t* delim, int64_t delim_len, int skip_empty,
+                              ovtk_string_split_out* out, int mem, int device, void* stream);
+int ovtk_contrib_string_join(const ovtk_strings* in, const int64_t* shape, int rank, const uint8_t* sep, int64_t sep_len, int64_t axis,
+                             ovtk_strings_out* out, int64_t* n_out, int mem, int device, void* stream);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py)
  * With profiling on, every kernel launch of the library is bracketed by hipEvents on the stream it is
  * launched on; times are accumulated per kernel name after the call's own synchronisation. */

@@ -96,6 +96,11 @@ class StringsOut(C.Structure):
                 ("n_chars", C.c_int64)]
 
 
+class StringSplitOut(C.Structure):
+    _fields_ = [("indices", C.c_void_p), ("begins", C.c_void_p), ("ends", C.c_void_p), ("chars", C.c_void_p), ("dense_shape", C.c_void_p),
+                ("values_capacity", C.c_int64), ("chars_capacity", C.c_int64), ("n_values", C.c_int64), ("n_chars", C.c_int64)]
+
+
 class RaggedI32(C.Structure):
     _fields_ = [("begins", C.c_void_p), ("ends", C.c_void_p), ("data", C.c_void_p), ("n", C.c_int64),
                 ("n_data", C.c_int64)]
@@ -135,6 +140,7 @@ EXPORTS = [
     "ovtk_sp_detokenizer_create", "ovtk_sp_detokenizer_run", "ovtk_sp_detokenizer_bound", "ovtk_sp_detokenizer_destroy",
     "ovtk_sp_detokenizer_enqueue", "ovtk_sp_detokenizer_finish",
     "ovtk_string_to_hash_bucket", "ovtk_equal_str", "ovtk_ragged_to_ragged",
+    "ovtk_bytes_to_chars", "ovtk_chars_to_bytes", "ovtk_contrib_string_split", "ovtk_contrib_string_join",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -209,6 +215,12 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_string_to_hash_bucket.argtypes = [C.POINTER(Strings), C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.ovtk_equal_str.argtypes = [C.POINTER(Strings), C.POINTER(Strings), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p]
     lib.ovtk_ragged_to_ragged.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_bytes_to_chars.argtypes = [C.POINTER(RaggedStrings), C.c_void_p, C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_chars_to_bytes.argtypes = [C.POINTER(RaggedStrings), C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_contrib_string_split.argtypes = [C.POINTER(Strings), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(StringSplitOut),
+                                              C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_contrib_string_join.argtypes = [C.POINTER(Strings), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(StringsOut),
+                                             C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p]
     _cache[key] = lib
     return lib
 

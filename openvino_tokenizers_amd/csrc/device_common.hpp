@@ -58,6 +58,8 @@ constexpr uint32_t kFlagExactOverflow = 64u;    // exact-path piece list too sma
 constexpr uint32_t kFlagDidNotRun = 0x80000000u;  // host side only: what the pinned status block holds until compact_kernel has written it
 constexpr uint32_t kFlagTailPending = 128u;     // merge_kernel's folded tail left the exact pieces / row scan to separate launches
 constexpr uint32_t kFlagUnsorted = 256u;        // RaggedToRagged: a row id below the one before it
+constexpr uint32_t kFlagOverlap = 512u;         // BytesToChars / CharsToBytes: a row begins before the row in front of it ended
+constexpr uint32_t kFlagTooLong = 1024u;        // string_ops_kernels.hpp: the text of a call would reach 2^31 bytes (or values)
 
 __device__ __forceinline__ int lane_id() { return int(threadIdx.x) & (kWave - 1); }
 __device__ __forceinline__ int wave_in_block() { return int(threadIdx.x) >> 6; }

@@ -1226,6 +1226,144 @@ class RaggedToRagged(_Op):
         return [ob[:rows], oe[:rows]]
 
 
+def _lengths_sum(m, b, e):
+    """Sum of the strings' lengths (offsets need be neither ordered nor gap-free: not the size of chars)."""
+    return int((e.long() - b).clamp(min=0).sum()) if m.torch else int(np.maximum(e.astype(np.int64) - b, 0).sum())
+
+
+class BytesToChars(_Op):
+    """Reference: src/bytes_to_chars.cpp (evaluate :284-339).  Ragged strings (5, or 6 with skips) -> as many outputs: the row
+    offsets (and skips) pass through, every element's bytes go through GPT-2's bytes_to_unicode map, skipped elements are copied."""
+
+    def evaluate(self, inputs, chars_capacity=None):
+        if len(inputs) not in (5, 6):
+            raise L.OvtkError(L.E_ARG, "supported input sizes are 5 or 6")   # :276
+        m = _Mem(inputs[4])
+        rs, (rb, re_, b, e, c) = _ragged_in(m, inputs)
+        psk = None
+        if len(inputs) == 6:
+            _, psk = m.inp(inputs[5], "bool")
+        cap = 2 * _lengths_sum(m, b, e) if chars_capacity is None else int(chars_capacity)   # :299
+        ob, pob = m.alloc(len(b), "i32")
+        oe, poe = m.alloc(len(b), "i32")
+        oc, poc = m.alloc(cap, "u8")
+        out = L.StringsOut(pob, poe, poc, cap, 0)
+        rc = self._lib.ovtk_bytes_to_chars(C.byref(rs), psk, C.byref(out), m.mem, self.device, m.stream)
+        self.needed_chars = int(out.n_chars)
+        self._chk(rc)
+        return [inputs[0], inputs[1], ob[:len(b)], oe[:len(b)], oc[:out.n_chars]] + list(inputs[5:])
+
+
+class CharsToBytes(_Op):
+    """Reference: src/chars_to_bytes.cpp (evaluate :31-68).  Ragged strings (5) -> strings (3), one per row: the row's elements fused
+    and mapped back to bytes.  Text outside the map's 256 characters is OVTK_E_RANGE (include/ovtk_amd.h)."""
+
+    def evaluate(self, inputs, chars_capacity=None):
+        if len(inputs) != 5:
+            raise L.OvtkError(L.E_ARG, f"CharsToBytes takes a ragged string tensor (5 inputs), got {len(inputs)}")
+        m = _Mem(inputs[4])
+        rs, (rb, re_, b, e, c) = _ragged_in(m, inputs)
+        cap = _lengths_sum(m, b, e) if chars_capacity is None else int(chars_capacity)
+        ob, pob = m.alloc(len(rb), "i32")
+        oe, poe = m.alloc(len(rb), "i32")
+        oc, poc = m.alloc(cap, "u8")
+        out = L.StringsOut(pob, poe, poc, cap, 0)
+        rc = self._lib.ovtk_chars_to_bytes(C.byref(rs), C.byref(out), m.mem, self.device, m.stream)
+        self.needed_chars = int(out.n_chars)
+        self._chk(rc)
+        return [ob[:len(rb)], oe[:len(rb)], oc[:out.n_chars]]
+
+
+def _shape_arg(shape):
+    a = np.ascontiguousarray(shape, dtype=np.int64).reshape(-1)
+    return a, C.c_void_p(a.ctypes.data), len(a)
+
+
+class ContribStringSplit(_Op):
+    """Reference: src/contrib_string_ops.cpp (evaluate :225-343).  Inputs: begins, ends (any shape), chars, the delimiter (u8 bytes),
+    skip_empty (one element).  Outputs: indices i64 [N, rank + 1], the values' begins / ends [N] and chars, dense_shape i64 [rank + 1]."""
+
+    def evaluate(self, inputs, values_capacity=None, chars_capacity=None):
+        if len(inputs) != 5:
+            raise L.OvtkError(L.E_ARG, "ContribStringSplit expects 5 inputs")   # :227
+        m = _Mem(inputs[2])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        c, pc = m.inp(inputs[2], "u8")
+        delim = np.frombuffer(_bytes_of(inputs[3]), dtype=np.uint8)
+        skip = np.asarray(_host(inputs[4], np.uint8)).reshape(-1)
+        if skip.size != 1:
+            raise L.OvtkError(L.E_ARG, "ContribStringSplit skip_empty input must be a scalar (single element)")   # :241
+        shape, pshape, rank = _shape_arg(tuple(np.shape(inputs[0])))   # (not b's: a 0-d input comes back from m.inp with one dimension)
+        n = int(np.prod(shape, dtype=np.int64)) if rank else 1
+        total = _lengths_sum(m, b, e)
+        vcap = n + total if values_capacity is None else int(values_capacity)
+        ccap = total if chars_capacity is None else int(chars_capacity)
+        idx, pidx = m.alloc(vcap * (rank + 1), "i64")
+        vb, pvb = m.alloc(vcap, "i32")
+        ve, pve = m.alloc(vcap, "i32")
+        vc, pvc = m.alloc(ccap, "u8")
+        dense = np.zeros(rank + 1, dtype=np.int64)
+        out = L.StringSplitOut(pidx, pvb, pve, pvc, dense.ctypes.data, vcap, ccap, 0, 0)
+        s = L.Strings(pb, pe, pc, n, len(c))
+        rc = self._lib.ovtk_contrib_string_split(C.byref(s), pshape, rank, delim.ctypes.data if delim.size else None, C.c_int64(delim.size),
+                                                 int(skip[0] != 0), C.byref(out), m.mem, self.device, m.stream)
+        self.needed_values, self.needed_chars = int(out.n_values), int(out.n_chars)
+        self._chk(rc)
+        nv = out.n_values
+        return [idx[:nv * (rank + 1)].reshape(nv, rank + 1), vb[:nv], ve[:nv], vc[:out.n_chars], dense]
+
+
+class ContribStringJoin(_Op):
+    """Reference: src/contrib_string_ops.cpp (evaluate :62-199).  Inputs: begins, ends (any shape), chars, the separator (u8 bytes),
+    axis (one integer).  Outputs: begins, ends with the axis removed (rank <= 1: scalars) and chars."""
+
+    def evaluate(self, inputs, chars_capacity=None):
+        if len(inputs) != 5:
+            raise L.OvtkError(L.E_ARG, "ContribStringJoin expects 5 inputs")   # :64
+        m = _Mem(inputs[2])
+        b, pb = m.inp(inputs[0], "i32")
+        e, pe = m.inp(inputs[1], "i32")
+        c, pc = m.inp(inputs[2], "u8")
+        sep = np.frombuffer(_bytes_of(inputs[3]), dtype=np.uint8)
+        axis_in = np.asarray(_host(inputs[4], np.int64)).reshape(-1)
+        if axis_in.size != 1:
+            raise L.OvtkError(L.E_ARG, "ContribStringJoin axis input must be a scalar (single element)")   # :77
+        axis = int(axis_in[0])
+        in_shape = tuple(int(d) for d in np.shape(inputs[0]))
+        shape, pshape, rank = _shape_arg(in_shape)
+        n = int(np.prod(shape, dtype=np.int64)) if rank else 1
+        if rank and -rank <= axis < rank:
+            out_shape = in_shape[:axis % rank] + in_shape[axis % rank + 1:]
+        else:
+            out_shape = ()
+        n_result = int(np.prod(out_shape, dtype=np.int64))
+        seps = n_result * max(int(in_shape[axis % rank]) - 1, 0) if rank and -rank <= axis < rank else 0
+        cap = _lengths_sum(m, b, e) + seps * sep.size if chars_capacity is None else int(chars_capacity)
+        ob, pob = m.alloc(n_result, "i32")
+        oe, poe = m.alloc(n_result, "i32")
+        oc, poc = m.alloc(cap, "u8")
+        out = L.StringsOut(pob, poe, poc, cap, 0)
+        n_out = C.c_int64(0)
+        s = L.Strings(pb, pe, pc, n, len(c))
+        rc = self._lib.ovtk_contrib_string_join(C.byref(s), pshape, rank, sep.ctypes.data if sep.size else None, C.c_int64(sep.size), C.c_int64(axis),
+                                                C.byref(out), C.byref(n_out), m.mem, self.device, m.stream)
+        self.needed_chars = int(out.n_chars)
+        self._chk(rc)
+        return [ob[:n_out.value].reshape(out_shape), oe[:n_out.value].reshape(out_shape), oc[:out.n_chars]]
+
+
+class RaggedTensorPack(_Op):
+    """Reference: src/ragged_tensor_pack.cpp (evaluate :23-32).  Inputs: begins, ends, elements.  Output: a copy of the elements (the
+    reference's own implementation; the offsets are not applied).  No kernel: a copy in the memory the elements live in."""
+
+    def evaluate(self, inputs):
+        if len(inputs) != 3:
+            raise L.OvtkError(L.E_ARG, f"RaggedTensorPack takes begins, ends and elements, got {len(inputs)} inputs")
+        x = inputs[2]
+        return [x.clone() if _is_torch(x) else np.array(x, copy=True)]
+
+
 class NormalizeUnicode(CharsMapNormalization):
     """Reference: src/normalize_unicode.cpp (evaluate :32-62): the charsmap of `normalization_form` (NFC, NFD, NFKC, NFKD) with all three
     flags off.  Strings (3) [+ skips] -> strings (3) [+ skips].  `charsmap=`: the form's precompiled table (see CharsMapNormalization)."""

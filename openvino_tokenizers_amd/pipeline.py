@@ -16,7 +16,8 @@ through the C ABI, one library call per node -- what `core.add_extension()` + th
   Truncate CombineSegments Padding                              -> FusedEncodeTailStep        ovtk_encode_tail_run
   VocabDecoder [ByteFallback] FuzeRagged                        -> FusedDetokenizeStep        ovtk_detokenize_run
 
-and leaves every other step as it is -- the normalizers (CharsmapStep, NormalizeUnicode, CaseFoldStep, RegexNormalizationStep) and the detokenizer's RegexDecodingSteps among them: a chain behind them
+and leaves every other step as it is -- a RegexSplit / BPETokenizer pair with a BytesToCharsStep between them and a VocabDecoder with a
+CharsToBytesStep behind it (the old-style byte-level graphs, vocabulary in "chars" form) are no such sub-chain and run op by op; the normalizers (CharsmapStep, NormalizeUnicode, CaseFoldStep, RegexNormalizationStep) and the detokenizer's RegexDecodingSteps among them: a chain behind them
 is fused as if they were not there.  The rewritten list gives the same outputs as the original one (tests/test_pipeline_fuse.py:
 bit for bit, on BASELINE.json's configurations); adapter/fuse_pass.cpp is the same recogniser over ov::Node chains.
 """
@@ -413,6 +414,32 @@ class FuseStep(Step):
         assert kind == "token_strings"
         rb, re_, b, e, c = vals
         return "text", self.op.evaluate([rb, re_, b, e]) + [c]
+
+
+class BytesToCharsStep(Step):
+    """src/bytes_to_chars.cpp:284-339 (tokenizer_pipeline.py:783-785, and every byte-level BPE graph converted before the converter
+    folded the op away): between RegexSplit and a BPETokenizer whose vocabulary is in its "chars" form.  Skipped pieces stay bytes."""
+
+    def __init__(self, lib=None):
+        self.op = K.BytesToChars(lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "strings"
+        skips = vals[5] if len(vals) > 5 else None
+        out = self.op.evaluate(list(vals[:5]) + ([skips] if skips is not None else []))
+        return "strings", list(out[:5]) + [skips]
+
+
+class CharsToBytesStep(Step):
+    """src/chars_to_bytes.cpp:31-68: behind a VocabDecoder over a "chars"-form vocabulary -- a row's token strings become one string
+    of bytes (the step fuses the row itself: no FuseStep behind it)."""
+
+    def __init__(self, lib=None):
+        self.op = K.CharsToBytes(lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "token_strings"
+        return "text", self.op.evaluate(list(vals[:5]))
 
 
 # ---------------------------------------------------------------------------------------------------------------- fused steps

@@ -27,6 +27,10 @@ whole rows and over the batch split on whitespace (a division and a mask as the 
 against themselves, RaggedToRagged on the row id of every word, and UTF8Validate on the same batch in the same run -- it also reads
 every byte of the batch once: the yardstick for the whole-row hash.  The checks are tests/test_tf_string_ops.py's restatements on the
 first rows.
+
+--only-string-ops times BytesToChars (on the batch split by the GPT-2 pattern: the pieces a byte-level BPE graph hands it), CharsToBytes
+(on its output), ContribStringSplit (the rows on " ") and ContribStringJoin (that back, along the last axis of the padded [rows, most
+tokens] tensor), with UTF8Validate on the same batch in the same run.  The checks are tests/string_ops_ref.py on the first rows.
 """
 from __future__ import annotations
 
@@ -94,6 +98,7 @@ def main():
     ap.add_argument("--only-sentencepiece", action="store_true", help="the SentencepieceTokenizer rows and nothing else")
     ap.add_argument("--only-sp-detok", action="store_true", help="the two sentencepiece detokenizers beside ovtk_detokenize_run and nothing else")
     ap.add_argument("--only-tf-ops", action="store_true", help="StringToHashBucket, EqualStr, RaggedToRagged beside UTF8Validate and nothing else")
+    ap.add_argument("--only-string-ops", action="store_true", help="BytesToChars, CharsToBytes, ContribStringSplit, ContribStringJoin beside UTF8Validate and nothing else")
     ap.add_argument("--detok-rows", type=int, default=16384)
     ap.add_argument("--detok-seq", type=int, default=2048)
     ap.add_argument("--emu", action="store_true", help="the SIMT-emulator build on host arrays (a smoke test of this script; the times mean nothing)")
@@ -200,6 +205,53 @@ def main():
         timed("RaggedToRagged(row id of every word)", lambda: r2r.evaluate([rowids_d, np.array([n], np.int32)]), 4 * len(rowids) + 8 * n,
               lambda out: same([ref_r[0][:k - 1], ref_r[1][:k - 1]], [to_np(out[0])[:k - 1], to_np(out[1])[:k - 1]]),
               f"{len(rowids)} ids, batch_size {n}: a lane per id, run starts write")
+    def string_ops():
+        # ---- BytesToChars (src/bytes_to_chars.cpp:284-339), CharsToBytes (src/chars_to_bytes.cpp:31-68), ContribStringSplit / Join
+        # (src/contrib_string_ops.cpp:225-343, :62-199); UTF8Validate beside them: the same bytes read once and written once
+        from openvino_tokenizers_amd.ops import BytesToChars, CharsToBytes, ContribStringJoin, ContribStringSplit
+        from tests import string_ops_ref as R
+        uv = UTF8Validate(replace_mode=False, lib=lib)
+        timed("UTF8Validate(replace_mode=False), the yardstick", lambda: uv.evaluate(d[2:5]), 2 * n_c + 16 * n, None,
+              "reads every byte once and writes it once; count -> scan -> write, a wave per string")
+        rows = [bytes(c[int(b[i]):int(e[i])]) for i in range(k)]
+        pieces = RegexSplit("isolate", lib=lib).evaluate(d + [tok.pattern_u8()])[:5]
+        n_p = len(pieces[2])
+        prb, pre_ = to_np(pieces[0])[:k], to_np(pieces[1])[:k]
+        m = int(pre_[-1])
+        head_ref = R.bytes_to_chars(prb, pre_, to_np(pieces[2])[:m], to_np(pieces[3])[:m], c)
+        # every timed call is given its capacities: without them the mirror classes size the outputs themselves, a reduction over all
+        # offsets and a host wait per call that the yardstick does not pay
+        piece_bytes = int((to_np(pieces[3]).astype(np.int64) - to_np(pieces[2])).sum())
+        b2c = timed("BytesToChars(the batch split by the GPT-2 pattern)", lambda: BytesToChars(lib=lib).evaluate(list(pieces), chars_capacity=2 * piece_bytes), 2 * n_c + 16 * n_p,
+                    lambda out: same([head_ref[0], head_ref[1], head_ref[2]], [to_np(out[2])[:m], to_np(out[3])[:m], to_np(out[4])[:len(head_ref[2])]]),
+                    f"{n_p} pieces: cover -> count (a lane per piece) -> two scans -> a lane per input byte, 2 048 bytes per block")
+        timed("CharsToBytes(its output)", lambda: CharsToBytes(lib=lib).evaluate(list(b2c[:5]), chars_capacity=len(b2c[4])), 2 * n_c + 8 * n_p + 8 * n,
+              lambda out: [bytes(to_np(out[2])[x:y]) for x, y in zip(to_np(out[0])[:k], to_np(out[1])[:k])] == rows,
+              "the same passes backwards; every byte is checked against the map's 256 characters")
+        sp_in = d[2:5] + [np.frombuffer(b" ", np.uint8), np.asarray([0], np.uint8)]
+        head_sp = R.string_split(b[:k], e[:k], c, b" ", False)
+        nv = len(head_sp[1])
+        sized = ContribStringSplit(lib=lib)
+        sized.evaluate(sp_in)   # (untimed: the sizes the timed calls are given)
+        sp = timed('ContribStringSplit(rows, " ")', lambda: ContribStringSplit(lib=lib).evaluate(sp_in, values_capacity=sized.needed_values, chars_capacity=sized.needed_chars),
+                   2 * n_c + 8 * n,
+                   lambda out: same([head_sp[0], head_sp[1], head_sp[2], head_sp[3]], [to_np(out[0])[:nv], to_np(out[1])[:nv], to_np(out[2])[:nv], to_np(out[3])[:len(head_sp[3])]]),
+                   "a wave per row, 64 positions a step: occurrences by ballot -> two scans -> the same walk writes (+ 16 bytes of indices and 8 of offsets per token)")
+        idx, vb, ve, vc, dense = sp
+        most = int(dense[1])
+        if args.emu:
+            db, de = np.zeros((n, most), np.int32), np.zeros((n, most), np.int32)
+        else:
+            db, de = torch.zeros((n, most), dtype=torch.int32, device=dev), torch.zeros((n, most), dtype=torch.int32, device=dev)
+        db[idx[:, 0], idx[:, 1]], de[idx[:, 0], idx[:, 1]] = vb, ve
+        counts = np.bincount(to_np(idx[:, 0])[:nv], minlength=k)[:k]
+        jn_in = [db, de, vc, np.frombuffer(b" ", np.uint8), np.asarray([-1])]
+        timed(f"ContribStringJoin([rows, {most}], axis -1)", lambda: ContribStringJoin(lib=lib).evaluate(jn_in, chars_capacity=len(vc) + n * (most - 1)), 2 * n_c + 8 * n * most,
+              lambda out: [bytes(to_np(out[2])[x:y]) for x, y in zip(to_np(out[0])[:k], to_np(out[1])[:k])] == [r + b" " * int(most - q) for r, q in zip(rows, counts)],
+              "a wave per row: count, scan, then the wave copies element after element (padding slots are empty elements, a separator each)")
+    if args.only_string_ops:
+        string_ops()
+        return
     if args.only_tf_ops:
         tf_ops()
         return
