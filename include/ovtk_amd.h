@@ -784,6 +784,36 @@ int ovtk_contrib_string_split(const ovtk_strings* in, const int64_t* shape, int 
 int ovtk_contrib_string_join(const ovtk_strings* in, const int64_t* shape, int rank, const uint8_t* sep, int64_t sep_len, int64_t axis,
                              ovtk_strings_out* out, int64_t* n_out, int mem, int device, void* stream);
 
+/* ---------------------------------------------------------------- NumericToString
+ * ovtk_numeric_to_string replaces NumericToString::evaluate, src/numeric_to_string.cpp:18-92 (the op the reference's TensorFlow
+ * front end maps AsString onto).  Stateless; device kernels only.  in: n elements of `dtype` (aligned to the element's size), host
+ * or device memory like the outputs.  out->begins / out->ends [n], the texts back to back from 0 in element order, out->n_chars the
+ * last end.  The text of an element:
+ *   - i8 .. i64, u8 .. u64: std::to_string -- decimal, '-' in front of negatives, no padding;
+ *   - boolean (one byte): "true" if the byte is non-zero, else "false";
+ *   - f64: `ostream << x`, that is printf("%g") with precision 6 in the "C" locale: the six significant decimal digits of the exact
+ *     binary value, rounded half to even; with X the decimal exponent AFTER that rounding, fixed notation if -4 <= X < 6, otherwise
+ *     d.ddddde+XX (at least two exponent digits); trailing zeros of the fraction, and a point left bare, are dropped.  0.0 is "0",
+ *     -0.0 "-0", infinities "inf" / "-inf", a NaN "nan", or "-nan" with its sign bit set (as glibc prints it);
+ *   - f32: the float widened to double (exact), then as f64.
+ * Any other dtype is OVTK_E_ARG (the reference asserts, :88).  ovtk_numeric_to_string_bound(dtype, n) is n times the type's longest
+ * text (4, 6, 11, 20, 3, 5, 10, 20, 12, 13, 5 bytes in the order below), -1 for a bad dtype or n < 0; a smaller chars buffer is fine
+ * when the text fits: OVTK_E_CAPACITY otherwise, out->n_chars = the bytes the call needs, nothing written.  n == 0 returns without a
+ * launch; n whose bound reaches 2^31 bytes is OVTK_E_UNSUPPORTED: split the call. */
+#define OVTK_NUM_I8 0
+#define OVTK_NUM_I16 1
+#define OVTK_NUM_I32 2
+#define OVTK_NUM_I64 3
+#define OVTK_NUM_U8 4
+#define OVTK_NUM_U16 5
+#define OVTK_NUM_U32 6
+#define OVTK_NUM_U64 7
+#define OVTK_NUM_F32 8
+#define OVTK_NUM_F64 9
+#define OVTK_NUM_BOOL 10
+int ovtk_numeric_to_string(const void* in, int dtype, int64_t n, ovtk_strings_out* out, int mem, int device, void* stream);
+int64_t ovtk_numeric_to_string_bound(int dtype, int64_t n);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py)
  * With profiling on, every kernel launch of the library is bracketed by hipEvents on the stream it is
  * launched on; times are accumulated per kernel name after the call's own synchronisation. */

@@ -17,6 +17,8 @@ DEFAULT_LIB = _HERE / "csrc" / "build" / "libovtk_amd.so"
 OVTK_OK = 0
 E_ARG, E_CAPACITY, E_VOCAB, E_UNSUPPORTED, E_HIP, E_RANGE = -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
+# OVTK_NUM_*: the element types of ovtk_numeric_to_string
+NUM_I8, NUM_I16, NUM_I32, NUM_I64, NUM_U8, NUM_U16, NUM_U32, NUM_U64, NUM_F32, NUM_F64, NUM_BOOL = range(11)
 
 i32p = C.POINTER(C.c_int32)
 u8p = C.POINTER(C.c_uint8)
@@ -141,6 +143,7 @@ EXPORTS = [
     "ovtk_sp_detokenizer_enqueue", "ovtk_sp_detokenizer_finish",
     "ovtk_string_to_hash_bucket", "ovtk_equal_str", "ovtk_ragged_to_ragged",
     "ovtk_bytes_to_chars", "ovtk_chars_to_bytes", "ovtk_contrib_string_split", "ovtk_contrib_string_join",
+    "ovtk_numeric_to_string", "ovtk_numeric_to_string_bound",
     "ovtk_string_tensor_packed_bytes", "ovtk_string_tensor_unpack", "ovtk_string_tensor_pack",
     "ovtk_shard_exchange_create", "ovtk_shard_max_rows", "ovtk_shard_wire_bytes", "ovtk_shard_pack", "ovtk_shard_unpack",
     "ovtk_shard_exchange_destroy",
@@ -221,6 +224,9 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
                                               C.c_int, C.c_int, C.c_void_p]
     lib.ovtk_contrib_string_join.argtypes = [C.POINTER(Strings), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(StringsOut),
                                              C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_numeric_to_string.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(StringsOut), C.c_int, C.c_int, C.c_void_p]
+    lib.ovtk_numeric_to_string_bound.argtypes = [C.c_int, C.c_int64]
+    lib.ovtk_numeric_to_string_bound.restype = C.c_int64
     _cache[key] = lib
     return lib
 

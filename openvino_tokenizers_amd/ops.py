@@ -1353,6 +1353,44 @@ class ContribStringJoin(_Op):
         return [ob[:n_out.value].reshape(out_shape), oe[:n_out.value].reshape(out_shape), oc[:out.n_chars]]
 
 
+_NUM_TYPES = {"int8": L.NUM_I8, "int16": L.NUM_I16, "int32": L.NUM_I32, "int64": L.NUM_I64, "uint8": L.NUM_U8, "uint16": L.NUM_U16,
+              "uint32": L.NUM_U32, "uint64": L.NUM_U64, "float32": L.NUM_F32, "float64": L.NUM_F64, "bool": L.NUM_BOOL}
+
+
+class NumericToString(_Op):
+    """Reference: src/numeric_to_string.cpp (evaluate :18-92; TensorFlow's AsString).  Input: one numeric tensor of any shape -- i8..i64,
+    u8..u64, f32, f64 or boolean, the type taken from the array (np.bool_ / torch.bool: boolean).  Outputs: begins, ends in the input's
+    shape and chars: std::to_string of the integers, `ostream << x` (%g, precision 6) of the floats, "true" / "false"."""
+
+    def bound(self, dtype, n):
+        return int(self._lib.ovtk_numeric_to_string_bound(int(dtype), C.c_int64(int(n))))
+
+    def evaluate(self, inputs, chars_capacity=None):
+        if len(inputs) != 1:
+            raise L.OvtkError(L.E_ARG, f"NumericToString takes one tensor, got {len(inputs)} inputs")
+        x = inputs[0]
+        m = _Mem(x)
+        if m.torch:
+            x = x.contiguous()
+            name, ptr, shape, n = str(x.dtype).replace("torch.", ""), x.data_ptr(), tuple(x.shape), x.numel()
+        else:
+            x = np.ascontiguousarray(x.cpu().numpy() if _is_torch(x) else x)
+            name, ptr, shape, n = x.dtype.name, x.ctypes.data, x.shape, x.size
+        m.keep.append(x)
+        if name not in _NUM_TYPES:
+            raise L.OvtkError(L.E_ARG, f"[NumericToString] Unsupported input type: {name}")   # :88
+        dtype = _NUM_TYPES[name]
+        cap = self.bound(dtype, n) if chars_capacity is None else int(chars_capacity)
+        ob, pob = m.alloc(n, "i32")
+        oe, poe = m.alloc(n, "i32")
+        oc, poc = m.alloc(cap, "u8")
+        out = L.StringsOut(pob, poe, poc, cap, 0)
+        rc = self._lib.ovtk_numeric_to_string(C.c_void_p(ptr), dtype, C.c_int64(n), C.byref(out), m.mem, self.device, m.stream)
+        self.needed_chars = int(out.n_chars)
+        self._chk(rc)
+        return [ob[:n].reshape(shape), oe[:n].reshape(shape), oc[:out.n_chars]]
+
+
 class RaggedTensorPack(_Op):
     """Reference: src/ragged_tensor_pack.cpp (evaluate :23-32).  Inputs: begins, ends, elements.  Output: a copy of the elements (the
     reference's own implementation; the offsets are not applied).  No kernel: a copy in the memory the elements live in."""

@@ -31,6 +31,11 @@ first rows.
 --only-string-ops times BytesToChars (on the batch split by the GPT-2 pattern: the pieces a byte-level BPE graph hands it), CharsToBytes
 (on its output), ContribStringSplit (the rows on " ") and ContribStringJoin (that back, along the last axis of the padded [rows, most
 tokens] tensor), with UTF8Validate on the same batch in the same run.  The checks are tests/string_ops_ref.py on the first rows.
+
+--only-numeric times NumericToString, one call per element type on 8 M values (--numeric-n): uniformly random bit patterns for f32 and
+f64 (f64 once more with OVTK_NUM2STR_EXACT=1: every finite value through the exact big-integer comparison), values of a uniformly
+random bit length for the integers, random bytes for boolean, and the batch's own token ids (the fused GPT-2 encode) as a realistic i32
+column; UTF8Validate on the batch in the same run is the yardstick.  The checks are Python's '%g' and str on the first elements.
 """
 from __future__ import annotations
 
@@ -99,6 +104,8 @@ def main():
     ap.add_argument("--only-sp-detok", action="store_true", help="the two sentencepiece detokenizers beside ovtk_detokenize_run and nothing else")
     ap.add_argument("--only-tf-ops", action="store_true", help="StringToHashBucket, EqualStr, RaggedToRagged beside UTF8Validate and nothing else")
     ap.add_argument("--only-string-ops", action="store_true", help="BytesToChars, CharsToBytes, ContribStringSplit, ContribStringJoin beside UTF8Validate and nothing else")
+    ap.add_argument("--only-numeric", action="store_true", help="NumericToString per element type beside UTF8Validate and nothing else")
+    ap.add_argument("--numeric-n", type=int, default=8 << 20)
     ap.add_argument("--detok-rows", type=int, default=16384)
     ap.add_argument("--detok-seq", type=int, default=2048)
     ap.add_argument("--emu", action="store_true", help="the SIMT-emulator build on host arrays (a smoke test of this script; the times mean nothing)")
@@ -249,6 +256,59 @@ def main():
         timed(f"ContribStringJoin([rows, {most}], axis -1)", lambda: ContribStringJoin(lib=lib).evaluate(jn_in, chars_capacity=len(vc) + n * (most - 1)), 2 * n_c + 8 * n * most,
               lambda out: [bytes(to_np(out[2])[x:y]) for x, y in zip(to_np(out[0])[:k], to_np(out[1])[:k])] == [r + b" " * int(most - q) for r, q in zip(rows, counts)],
               "a wave per row: count, scan, then the wave copies element after element (padding slots are empty elements, a separator each)")
+    def numeric_ops():
+        # ---- NumericToString (src/numeric_to_string.cpp:18-92); UTF8Validate beside it: the other count -> scan -> write op
+        from openvino_tokenizers_amd.ops import NumericToString
+        uv = UTF8Validate(replace_mode=False, lib=lib)
+        timed("UTF8Validate(replace_mode=False), the yardstick", lambda: uv.evaluate(d[2:5]), 2 * n_c + 16 * n, None,
+              "reads every byte once and writes it once; count -> scan -> write, a wave per string")
+        m = args.numeric_n
+        rng_n = np.random.default_rng(14)
+        op = NumericToString(lib=lib)
+
+        def column(name, arr, want, note, env=None):
+            arr_d = arr if args.emu else torch.as_tensor(arr, device=dev)
+            cap = op.bound(L.NUM_I8 + ["int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64", "float32", "float64", "bool"].index(arr.dtype.name), arr.size)
+            texts = [want(v) for v in arr[:k].tolist()]
+            ends = np.cumsum([len(t) for t in texts]).astype(np.int32)
+            probe = op.evaluate([arr_d], chars_capacity=cap)
+            n_text = len(probe[2])
+            knob = os.environ.get("OVTK_NUM2STR_EXACT")
+            if env:
+                os.environ["OVTK_NUM2STR_EXACT"] = env
+            try:
+                timed(name, lambda: op.evaluate([arr_d], chars_capacity=cap), arr.nbytes + 8 * arr.size + n_text,
+                      lambda out: same([ends, np.frombuffer(b"".join(texts), np.uint8)], [to_np(out[1])[:k], to_np(out[2])[:int(ends[-1])]]),
+                      f"{arr.size} values, {n_text} bytes of text; {note}")
+            finally:
+                if env:
+                    if knob is None:
+                        del os.environ["OVTK_NUM2STR_EXACT"]
+                    else:
+                        os.environ["OVTK_NUM2STR_EXACT"] = knob
+
+        def pct(v):
+            return (("%g" % v) if v == v else ("-nan" if np.signbit(v) else "nan")).encode()
+        f64 = rng_n.integers(0, 1 << 64, m, dtype=np.uint64).view(np.float64)
+        f32 = rng_n.integers(0, 1 << 32, m, dtype=np.uint64).astype(np.uint32).view(np.float32)
+        column("NumericToString(f64, random bit patterns)", f64, pct, "192-bit product per value; count formats, write formats again")
+        column("NumericToString(f64, random bit patterns, exact path forced)", f64, pct, "OVTK_NUM2STR_EXACT=1: the big-integer comparison for every finite value", env="1")
+        column("NumericToString(f32, random bit patterns)", f32, pct, "widened on the bits, then the f64 path")
+        for name in ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64"):
+            info = np.iinfo(name)
+            bits = rng_n.integers(0, info.bits + 1, m).astype(np.uint64)
+            mag = rng_n.integers(0, 1 << 64, m, dtype=np.uint64) >> (np.uint64(64) - np.maximum(bits, 1))
+            mag[bits == 0] = 0
+            arr = mag.astype(name) if info.min == 0 else (mag >> np.uint64(1)).astype(np.int64).astype(name) * rng_n.choice(np.array([-1, 1], name), m)
+            column(f"NumericToString({name}, a uniformly random bit length)", arr, lambda v: str(v).encode(), "digit count from the bit length; two digits per division by 100")
+        column("NumericToString(boolean, random bytes)", (rng_n.integers(0, 256, m, dtype=np.uint8) * rng_n.integers(0, 2, m, dtype=np.uint8)).view(np.bool_),
+               lambda v: b"true" if v else b"false", "a byte in, 4 or 5 out")
+        fused = FusedSplitBPE(RegexSplit("isolate", lib=lib), BPETokenizer(**tok.attrs, lib=lib))
+        ids = to_np(fused.evaluate(d + [tok.pattern_u8()], tok.consts)[2]).astype(np.int32)
+        column("NumericToString(i32, the batch's token ids)", ids, lambda v: str(v).encode(), "GPT-2 ids: 1 to 5 digits")
+    if args.only_numeric:
+        numeric_ops()
+        return
     if args.only_string_ops:
         string_ops()
         return
