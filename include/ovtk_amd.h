@@ -273,6 +273,38 @@ int ovtk_encode_dense_enqueue(ovtk_special_tokens_split* special, ovtk_regex_spl
                               const uint8_t* skips, const ovtk_dense_params* params, int32_t* out_ids, uint8_t* out_mask, int64_t capacity,
                               void* stream, ovtk_pending** pending);
 int ovtk_encode_dense_finish(ovtk_pending* pending, int32_t* width, int64_t* n_ids);
+/* Paired input in ONE call: the graph the reference's add_second_input builds (python/openvino_tokenizers/
+ * tokenizer_transformations.py:22-304) -- the two string inputs concatenated, the front of the graph on all of their rows, the ragged
+ * ids sliced back into two halves -> Truncate with two inputs (src/truncate.cpp:69-144) -> CombineSegments with five segments and
+ * their type ids (src/combine_segments.cpp:36-134) -> RaggedToDense x 3 (src/ragged_to_dense.cpp:70-174) = input_ids i32[n, T],
+ * attention_mask u8[n, T], token_type_ids i32[n, T].  `in` holds n_first + n_second rows, the first sequences in front; this form
+ * needs n_first == n_second >= 0 (1 against n, or an empty second input: ovtk_encode_run / ovtk_wordpiece_encode_run on all rows,
+ * then ovtk_encode_tail_run over the two halves -- OVTK_E_ARG says so).  Dense row i = front | row i cut | between | row n + i cut |
+ * behind, written by the encode's last pass; no ragged ids tensor exists.  Same values as that two-call form.  Device buffers;
+ * out_mask and out_type_ids may be NULL.  More than 4 constants in a slot: OVTK_E_UNSUPPORTED; an unknown trunc_mode: OVTK_E_ARG.
+ * Both are completed by ovtk_encode_pair_dense_finish, which reports T (target_dim < 0: the longest combined row) and the number of
+ * ids before truncation; OVTK_E_CAPACITY when n * T exceeds `capacity` cells (*width = the T it needs). */
+typedef struct {
+    int32_t max_length;        /* what Truncate receives: the ids of a pair that stay (the added constants already subtracted) */
+    int trunc_left;            /* 0 "right": the first ids stay; 1 "left": the last */
+    int trunc_mode;            /* 0 only_first, 1 only_second, 2 longest_first (truncate.cpp:82-143) */
+    int pad_right;             /* RaggedToDense pad_right */
+    int32_t pad_value;         /* input_ids padding (attention_mask pads with 0) */
+    int32_t type_pad_value;    /* token_type_ids padding */
+    int32_t target_dim;        /* row width; < 0: the longest combined row (the PaddingStep's ReduceMax) */
+    const int32_t* front;      /* HOST memory: constant ids in front of the first sequence (at most 4) */
+    int n_front;
+    const int32_t* between;    /* ... between the two sequences (at most 4) */
+    int n_between;
+    const int32_t* behind;     /* ... and behind the second one (at most 4) */
+    int n_behind;
+    int32_t type_ids[5];       /* CombineSegments' ids of front, first, between, second, behind */
+} ovtk_pair_dense_params;
+int ovtk_encode_pair_dense_enqueue(ovtk_special_tokens_split* special, ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in,
+                                   const uint8_t* skips, int64_t n_first, const ovtk_pair_dense_params* params, int32_t* out_ids,
+                                   uint8_t* out_mask, int32_t* out_type_ids, int64_t capacity, void* stream, ovtk_pending** pending);
+/* (tokenizer_transformations.py:22-304: the paired graph's outputs are complete; also for ovtk_wordpiece_encode_pair_dense_enqueue) */
+int ovtk_encode_pair_dense_finish(ovtk_pending* pending, int32_t* width, int64_t* n_ids);
 int ovtk_encode_enqueue(ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
                         const ovtk_ragged_i32_out* out, void* stream, ovtk_pending** pending);
 int ovtk_encode_finish(ovtk_pending* pending, ovtk_ragged_i32_out* out);
@@ -327,6 +359,13 @@ int ovtk_wordpiece_encode_run(ovtk_wordpiece* h, ovtk_regex_split* whitespace, o
 int ovtk_wordpiece_encode_enqueue(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk_regex_split* delimiters,
                                   const ovtk_ragged_strings* in, int32_t unk_token_id, const ovtk_ragged_i32_out* out,
                                   void* stream, ovtk_pending** pending);
+/* Paired input: the BERT chain of ovtk_wordpiece_encode_run in front of the tail of ovtk_encode_pair_dense_enqueue (the reference's
+ * add_second_input, python/openvino_tokenizers/tokenizer_transformations.py:22-304; src/truncate.cpp:69-144).  Same contract; completed
+ * by ovtk_encode_pair_dense_finish. */
+int ovtk_wordpiece_encode_pair_dense_enqueue(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk_regex_split* delimiters,
+                                             const ovtk_ragged_strings* in, int32_t unk_token_id, int64_t n_first,
+                                             const ovtk_pair_dense_params* params, int32_t* out_ids, uint8_t* out_mask,
+                                             int32_t* out_type_ids, int64_t capacity, void* stream, ovtk_pending** pending);
 void ovtk_wordpiece_destroy(ovtk_wordpiece* h);
 
 /* ---------------------------------------------------------------- VocabEncoder

@@ -6,5 +6,5 @@ Compute happens only in csrc/build/libovtk_amd.so (hand-written HIP for gfx950) 
 include/ovtk_amd.h; see DESIGN.md and INTEGRATION.md.
 """
 from ._lib import OvtkError, load  # noqa: F401
-from .ops import (BPETokenizer, ByteFallback, BytesToChars, CaseFold, CharsMapNormalization, CharsToBytes, CombineSegments, ContribStringJoin, ContribStringSplit, EqualStr, FusedDetokenizer, FusedEncodeDense, FusedEncodeTail, FusedSpecialSplitBPE, FusedSplitBPE, FusedSplitWordpiece, FuzeRagged, NormalizeUnicode, RaggedTensorPack, RaggedToDense, RaggedToRagged, RaggedToSparse,  # noqa: F401
+from .ops import (BPETokenizer, ByteFallback, BytesToChars, CaseFold, CharsMapNormalization, CharsToBytes, CombineSegments, ContribStringJoin, ContribStringSplit, EqualStr, FusedDetokenizer, FusedEncodeDense, FusedEncodeTail, FusedPairEncodeDense, FusedPairWordpieceDense, FusedSpecialSplitBPE, FusedSplitBPE, FusedSplitWordpiece, FuzeRagged, NormalizeUnicode, RaggedTensorPack, RaggedToDense, RaggedToRagged, RaggedToSparse,  # noqa: F401
                   RegexNormalization, RegexSplit, SentencepieceDetokenizer, SentencepieceStreamDetokenizer, SentencepieceTokenizer, SpecialTokensSplit, StringTensorPack, StringTensorUnpack, StringToHashBucket, TrieTokenizer, Truncate, UnigramTokenizer, UTF8Validate, VocabDecoder, VocabEncoder, WordpieceTokenizer)

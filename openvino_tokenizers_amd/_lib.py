@@ -119,6 +119,12 @@ class DenseParams(C.Structure):
                 ("prefix", C.c_void_p), ("n_prefix", C.c_int), ("suffix", C.c_void_p), ("n_suffix", C.c_int)]
 
 
+class PairDenseParams(C.Structure):
+    _fields_ = [("max_length", C.c_int32), ("trunc_left", C.c_int), ("trunc_mode", C.c_int), ("pad_right", C.c_int), ("pad_value", C.c_int32),
+                ("type_pad_value", C.c_int32), ("target_dim", C.c_int32), ("front", C.c_void_p), ("n_front", C.c_int),
+                ("between", C.c_void_p), ("n_between", C.c_int), ("behind", C.c_void_p), ("n_behind", C.c_int), ("type_ids", C.c_int32 * 5)]
+
+
 class ShardResult(C.Structure):
     _fields_ = [("n_ids", C.c_int64), ("max_shard_ids", C.c_int64), ("status", C.c_int64), ("reserved", C.c_int64)]
 
@@ -127,8 +133,8 @@ EXPORTS = [
     "ovtk_last_error", "ovtk_abi_version", "ovtk_device_name",
     "ovtk_regex_split_create", "ovtk_regex_split_run", "ovtk_regex_split_destroy",
     "ovtk_special_tokens_split_create", "ovtk_special_tokens_split_run", "ovtk_special_tokens_split_destroy",
-    "ovtk_bpe_create", "ovtk_bpe_run", "ovtk_bpe_destroy", "ovtk_bpe_memo_entries", "ovtk_set_memo_store", "ovtk_bpe_store_entries", "ovtk_encode_run", "ovtk_encode_special_run", "ovtk_encode_special_enqueue", "ovtk_encode_dense_enqueue", "ovtk_encode_dense_finish", "ovtk_encode_enqueue", "ovtk_encode_enqueue_host", "ovtk_encode_enqueue_packed", "ovtk_encode_enqueue_wire", "ovtk_encode_finish", "ovtk_set_row_tickets", "ovtk_set_short_path", "ovtk_short_path_stats",
-    "ovtk_wordpiece_create", "ovtk_wordpiece_run", "ovtk_wordpiece_encode_run", "ovtk_wordpiece_encode_enqueue", "ovtk_wordpiece_destroy",
+    "ovtk_bpe_create", "ovtk_bpe_run", "ovtk_bpe_destroy", "ovtk_bpe_memo_entries", "ovtk_set_memo_store", "ovtk_bpe_store_entries", "ovtk_encode_run", "ovtk_encode_special_run", "ovtk_encode_special_enqueue", "ovtk_encode_dense_enqueue", "ovtk_encode_dense_finish", "ovtk_encode_pair_dense_enqueue", "ovtk_encode_pair_dense_finish", "ovtk_encode_enqueue", "ovtk_encode_enqueue_host", "ovtk_encode_enqueue_packed", "ovtk_encode_enqueue_wire", "ovtk_encode_finish", "ovtk_set_row_tickets", "ovtk_set_short_path", "ovtk_short_path_stats",
+    "ovtk_wordpiece_create", "ovtk_wordpiece_run", "ovtk_wordpiece_encode_run", "ovtk_wordpiece_encode_enqueue", "ovtk_wordpiece_encode_pair_dense_enqueue", "ovtk_wordpiece_destroy",
     "ovtk_vocab_encoder_create", "ovtk_vocab_encoder_run", "ovtk_vocab_encoder_destroy",
     "ovtk_ragged_to_dense",
     "ovtk_vocab_decoder_create", "ovtk_vocab_decoder_run", "ovtk_vocab_decoder_destroy",

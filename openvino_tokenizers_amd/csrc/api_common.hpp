@@ -403,6 +403,8 @@ struct ovtk_pending {
     std::unique_ptr<ovtk::PendingStrings> strings;
     ovtk_strings_out strings_out{};
     std::shared_ptr<int32_t> dense_width;   // ovtk_encode_dense_enqueue: the row width, known when the run has finished
+    int late_rc = 0;                        // a verdict made at enqueue that finish reports (ovtk_encode_pair_dense_finish: OVTK_E_CAPACITY
+    std::string late_msg;                   // of a batch without text, so that the caller gets the width it needs)
 };
 namespace ovtk {
 
@@ -495,6 +497,14 @@ public:
     void output_dense(const DenseSink& dense) {
         dense_ = dense;
         dense_on_ = true;
+        small_ok_ = false;
+    }
+    // The result leaves as input_ids / attention_mask / token_type_ids [n_rows / 2, T] (device memory): PairDenseSink, the paired graph's
+    // tail in compact_kernel.  The run's rows are the first sequences followed by as many second ones.
+    void output_pair_dense(const PairDenseSink& pair) {
+        pair_ = pair;
+        pair_on_ = true;
+        dense_on_ = true;   // (no ragged outputs, no one-launch form, the width redone by the short path's second set of launches)
         small_ok_ = false;
     }
 
@@ -793,7 +803,13 @@ private:
         const RaggedSink rsink{d_ids_, d_begins_, d_ends_};
         with_bool(plan_.stage16, [&](auto s16) {
             constexpr bool S16 = decltype(s16)::value;
-            if (dense_on_) {
+            if (pair_on_) {
+                PairDenseSink pair = pair_;
+                pair.row_cnt = w.row_cnt;
+                pair.n = n_rows_ / 2;
+                OVTK_LAUNCH(ws.marks, "pair_width", pair_width_kernel, std::min(64, (pair.n + kBlockThreads - 1) / kBlockThreads), kBlockThreads, s_, n_rows_, w, pair);
+                OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<PairDenseSink, S16>), cgrid, kBlockThreads, s_, n_rows_, w, pair);
+            } else if (dense_on_) {
                 OVTK_LAUNCH(ws.marks, "row_width", row_width_kernel, std::min(64, (n_rows_ + kBlockThreads - 1) / kBlockThreads), kBlockThreads, s_, n_rows_, w, dense_);
                 OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<DenseSink, S16>), cgrid, kBlockThreads, s_, n_rows_, w, dense_);
             } else if (wire_.hdr) OVTK_LAUNCH(ws.marks, "compact", (compact_kernel<WireSink, S16>), cgrid, kBlockThreads, s_, n_rows_, w, wire_);
@@ -841,6 +857,8 @@ private:
     WireSink wire_{};
     DenseSink dense_{};
     bool dense_on_ = false;
+    PairDenseSink pair_{};
+    bool pair_on_ = false;
     std::function<void(const RunStatus&)> on_status_;
     RowsIn d_in_{};
     int n_rows_ = 0, grid_ = 0, n_tiles_ = 0;
@@ -853,6 +871,74 @@ std::unique_ptr<RowsRun<std::decay_t<Middle>>> make_rows_run(int device, const c
                                                              const uint8_t* skips, int mul, const ovtk_ragged_i32_out* out, int mem,
                                                              hipStream_t s, Middle&& middle, const EncodePlan* plan = nullptr) {
     return std::make_unique<RowsRun<std::decay_t<Middle>>>(device, op, in, skips, mul, out, mem, s, std::forward<Middle>(middle), plan);
+}
+
+// The arguments of the paired one-call encodes (ovtk_encode_pair_dense_enqueue, ovtk_wordpiece_encode_pair_dense_enqueue) -> the sink.
+inline int pair_sink_from_params(const char* op, const ovtk_ragged_strings* in, int64_t n_first, const ovtk_pair_dense_params* p, int32_t* out_ids,
+                                 uint8_t* out_mask, int32_t* out_type_ids, int64_t capacity, PairDenseSink& d) {
+    const std::string name(op);
+    if (!p || !out_ids || !in || capacity < 0) return set_error(OVTK_E_ARG, name + ": null argument");
+    if (n_first < 0 || in->n_rows - n_first != n_first)
+        return set_error(OVTK_E_ARG, name + ": the one call takes as many second rows as first ones (" + std::to_string(n_first) + " + " +
+                                         std::to_string(in->n_rows - n_first) +
+                                         "); 1 against n or an empty second input: the two-call form (the encode on all rows, then ovtk_encode_tail_run over the halves)");
+    if (p->n_front < 0 || p->n_between < 0 || p->n_behind < 0 || (p->n_front && !p->front) || (p->n_between && !p->between) ||
+        (p->n_behind && !p->behind) || p->max_length < 0)
+        return set_error(OVTK_E_ARG, name + ": bad constant ids or max_length < 0");
+    if (p->n_front > kDenseAffix || p->n_between > kDenseAffix || p->n_behind > kDenseAffix)
+        return set_error(OVTK_E_UNSUPPORTED, name + ": at most 4 constant ids in front / between / behind");
+    if (p->trunc_mode < 0 || p->trunc_mode > 2) return set_error(OVTK_E_ARG, name + ": Unknown truncation mode: " + std::to_string(p->trunc_mode));
+    d = PairDenseSink{};
+    d.ids = out_ids;
+    d.mask = out_mask;
+    d.types = out_type_ids;
+    d.capacity = capacity;
+    d.n = int32_t(n_first);
+    d.max_length = p->max_length;
+    d.trunc_left = p->trunc_left ? 1 : 0;
+    d.mode = p->trunc_mode;
+    d.pad_right = p->pad_right ? 1 : 0;
+    d.pad_value = p->pad_value;
+    d.type_pad = p->type_pad_value;
+    d.target_dim = p->target_dim;
+    d.n_front = p->n_front;
+    d.n_between = p->n_between;
+    d.n_behind = p->n_behind;
+    for (int i = 0; i < d.n_front; ++i) d.front[i] = p->front[i];
+    for (int i = 0; i < d.n_between; ++i) d.between[i] = p->between[i];
+    for (int i = 0; i < d.n_behind; ++i) d.behind[i] = p->behind[i];
+    for (int i = 0; i < 5; ++i) d.type_ids[i] = p->type_ids[i];
+    return OVTK_OK;
+}
+// A paired batch without text (the all-empty quirk of regex_split.cpp:129-143 is the ragged tensor's; the dense tensors keep their
+// rows): every row is the constant segments and padding -- T cells of which the host knows everything.
+inline int pair_rows_without_text(const PairDenseSink& d, int device, hipStream_t s, ovtk_pending& p) {
+    const int32_t len = d.n_front + d.n_between + d.n_behind, T = d.target_dim >= 0 ? d.target_dim : (d.n > 0 ? len : 0);   // (no row: no longest row)
+    *p.dense_width = T;
+    if (int64_t(d.n) * T > d.capacity) {   // (reported by finish, with the width, as for a batch with text)
+        p.late_rc = OVTK_E_CAPACITY;
+        p.late_msg = "encode_pair_dense: dense outputs too small (row width " + std::to_string(T) + ")";
+        return OVTK_OK;
+    }
+    if (T <= 0 || d.n <= 0) return OVTK_OK;
+    const size_t cells = size_t(d.n) * size_t(T);
+    std::vector<int32_t> ids(cells, d.pad_value), types(d.types ? cells : 0, d.type_pad);
+    std::vector<uint8_t> mask(d.mask ? cells : 0, 0);
+    const int col0 = d.pad_right ? 0 : std::max(0, T - len);
+    for (int64_t r = 0; r < d.n; ++r)
+        for (int k = 0; k < len && col0 + k < T; ++k) {
+            const bool f = k < d.n_front, b = !f && k < d.n_front + d.n_between;
+            const size_t at = size_t(r) * size_t(T) + size_t(col0 + k);
+            ids[at] = f ? d.front[k] : (b ? d.between[k - d.n_front] : d.behind[k - d.n_front - d.n_between]);
+            if (d.types) types[at] = f ? d.type_ids[0] : (b ? d.type_ids[2] : d.type_ids[4]);
+            if (d.mask) mask[at] = 1;
+        }
+    OVTK_HIP(hipSetDevice(device));
+    OVTK_HIP(hipMemcpyAsync(d.ids, ids.data(), cells * 4, hipMemcpyHostToDevice, s));
+    if (d.mask) OVTK_HIP(hipMemcpyAsync(d.mask, mask.data(), cells, hipMemcpyHostToDevice, s));
+    if (d.types) OVTK_HIP(hipMemcpyAsync(d.types, types.data(), cells * 4, hipMemcpyHostToDevice, s));
+    OVTK_HIP(hipStreamSynchronize(s));   // (the host vectors are read by then)
+    return OVTK_OK;
 }
 
 // The synchronous form every *_run entry point uses.  `middle` is copied: capture by value.

@@ -948,7 +948,7 @@ void note_store_use(const ovtk_bpe* bpe, const RunStatus& st) {
 int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ovtk_ragged_strings* in, const uint8_t* skips,
                  ovtk_ragged_i32_out* out, int mem, void* stream, std::unique_ptr<PendingRun>& run, const WireSink* wire = nullptr,
                  std::shared_ptr<void> device_inputs = nullptr, const ovtk_special_tokens_split* special = nullptr,
-                 const DenseSink* dense = nullptr, std::shared_ptr<int32_t> dense_width = nullptr) {
+                 const DenseSink* dense = nullptr, std::shared_ptr<int32_t> dense_width = nullptr, const PairDenseSink* pair = nullptr) {
     // device_inputs: `in` names device memory whatever `mem` says about the outputs (ovtk_encode_enqueue_packed: the packed
     // batch was copied to the device by the caller of this function); the object owns that memory until the run is over.
     const int in_mem = device_inputs ? OVTK_MEM_DEVICE : mem;
@@ -1061,6 +1061,7 @@ int start_encode(const ovtk_regex_split* split_in, const ovtk_bpe* bpe, const ov
         });
     if (wire) r->output_to_wire(*wire);
     if (dense) r->output_dense(*dense);
+    if (pair) r->output_pair_dense(*pair);
     if (int rc = r->start()) return rc;
     run = std::move(r);
     return OVTK_OK;
@@ -1190,10 +1191,36 @@ int ovtk_encode_dense_finish(ovtk_pending* pending, int32_t* width, int64_t* n_i
     std::unique_ptr<ovtk_pending> p(pending);
     int rc = OVTK_OK;
     if (p->run) rc = p->run->finish(&p->out);
+    else if (p->late_rc) rc = set_error(p->late_rc, p->late_msg);
     if (width) *width = p->dense_width ? *p->dense_width : 0;
     if (n_ids) *n_ids = p->out.n_data;
     return rc;
 }
+
+int ovtk_encode_pair_dense_enqueue(ovtk_special_tokens_split* special, ovtk_regex_split* split, ovtk_bpe* bpe, const ovtk_ragged_strings* in,
+                                   const uint8_t* skips, int64_t n_first, const ovtk_pair_dense_params* params, int32_t* out_ids,
+                                   uint8_t* out_mask, int32_t* out_type_ids, int64_t capacity, void* stream, ovtk_pending** pending) {
+    if (!pending || !bpe) return set_error(OVTK_E_ARG, "encode_pair_dense: null argument");
+    if (!split) return set_error(OVTK_E_ARG, "null split handle");
+    PairDenseSink d{};
+    if (int rc = pair_sink_from_params("encode_pair_dense", in, n_first, params, out_ids, out_mask, out_type_ids, capacity, d)) return rc;
+    if (int rc = check_rows(in)) return rc;
+    auto p = std::make_unique<ovtk_pending>();
+    p->dense_width = std::make_shared<int32_t>(params->target_dim < 0 ? 0 : params->target_dim);
+    p->out = ovtk_ragged_i32_out{nullptr, nullptr, nullptr, INT32_MAX - 2, 0, 0};   // (no ragged ids: nothing of that kind overflows)
+    if (in->strings.n_chars == 0 || in->n_rows == 0) {
+        if (int rc = pair_rows_without_text(d, bpe->device, static_cast<hipStream_t>(stream), *p)) return rc;
+        p->out.n_rows = in->n_rows;
+        *pending = p.release();
+        return OVTK_OK;
+    }
+    if (int rc = start_encode(split, bpe, in, skips, &p->out, OVTK_MEM_DEVICE, stream, p->run, nullptr, nullptr, special, nullptr, p->dense_width, &d))
+        return rc;
+    *pending = p.release();
+    return OVTK_OK;
+}
+
+int ovtk_encode_pair_dense_finish(ovtk_pending* pending, int32_t* width, int64_t* n_ids) { return ovtk_encode_dense_finish(pending, width, n_ids); }
 
 int ovtk_set_short_path(int mode) {
     if (mode < 0 || mode > 2) return set_error(OVTK_E_ARG, "short path: 0 (never), 1 (where a handle's last calls say it works), 2 (every eligible call tries)");

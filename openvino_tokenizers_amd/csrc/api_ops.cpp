@@ -229,7 +229,8 @@ struct WordpieceKernels {
 // Launches the fused BERT split + WordPiece kernels; `run` stays empty when the result was complete without any.
 int start_wordpiece_encode(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk_regex_split* delimiters,
                            const ovtk_ragged_strings* in, int32_t unk_token_id, ovtk_ragged_i32_out* out, int mem,
-                           void* stream, std::unique_ptr<PendingRun>& run) {
+                           void* stream, std::unique_ptr<PendingRun>& run, const PairDenseSink* pair = nullptr,
+                           std::shared_ptr<int32_t> pair_width = nullptr) {
     if (int rc = check_rows(in)) return rc;
     if (!h || !whitespace || !delimiters || !out) return set_error(OVTK_E_ARG, "null argument");
     if (whitespace->dev.kind != kSplitWhitespace || whitespace->dev.drop != 1 || whitespace->max_splits != -1 ||
@@ -269,10 +270,15 @@ int start_wordpiece_encode(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk
     auto r = make_rows_run(h->device, "WordpieceTokenizer", in, nullptr, 1, out, mem, s,
                            [k](Workspace& ws, const RowsIn& d_in, const EncodeWork& w, int grid) { launch_middle(k.plan, k, ws, d_in, w, grid); },
                            &plan);
-    if (plan.short_ok) {
-        r->expect(h->predict.arm(memo_only.store.slots != nullptr));
-        r->on_status([h](const RunStatus& st) { h->predict.note(st); });
+    if (plan.short_ok) r->expect(h->predict.arm(memo_only.store.slots != nullptr));
+    if (plan.short_ok || pair_width) {
+        const bool note = plan.short_ok;
+        r->on_status([h, note, pair_width](const RunStatus& st) {
+            if (pair_width) *pair_width = st.width;
+            if (note) h->predict.note(st);
+        });
     }
+    if (pair) r->output_pair_dense(*pair);
     if (int rc = r->start()) return rc;
     run = std::move(r);
     return OVTK_OK;
@@ -295,6 +301,30 @@ int ovtk_wordpiece_encode_enqueue(ovtk_wordpiece* h, ovtk_regex_split* whitespac
     return enqueue_pending(*out, pending, [&](ovtk_pending& p) {
         return start_wordpiece_encode(h, whitespace, delimiters, in, unk_token_id, &p.out, OVTK_MEM_DEVICE, stream, p.run);
     });
+}
+
+int ovtk_wordpiece_encode_pair_dense_enqueue(ovtk_wordpiece* h, ovtk_regex_split* whitespace, ovtk_regex_split* delimiters,
+                                             const ovtk_ragged_strings* in, int32_t unk_token_id, int64_t n_first,
+                                             const ovtk_pair_dense_params* params, int32_t* out_ids, uint8_t* out_mask,
+                                             int32_t* out_type_ids, int64_t capacity, void* stream, ovtk_pending** pending) {
+    if (!pending) return set_error(OVTK_E_ARG, "wordpiece_encode_pair_dense: null argument");
+    PairDenseSink d{};
+    if (int rc = pair_sink_from_params("wordpiece_encode_pair_dense", in, n_first, params, out_ids, out_mask, out_type_ids, capacity, d)) return rc;
+    auto p = std::make_unique<ovtk_pending>();
+    p->dense_width = std::make_shared<int32_t>(params->target_dim < 0 ? 0 : params->target_dim);
+    p->out = ovtk_ragged_i32_out{nullptr, nullptr, nullptr, INT32_MAX - 2, 0, 0};   // (no ragged ids: nothing of that kind overflows)
+    if (in->strings.n_chars == 0 || in->n_rows == 0) {
+        if (!h || !whitespace || !delimiters) return set_error(OVTK_E_ARG, "wordpiece_encode_pair_dense: null argument");
+        if (int rc = check_rows(in)) return rc;
+        if (int rc = pair_rows_without_text(d, h->device, static_cast<hipStream_t>(stream), *p)) return rc;
+        p->out.n_rows = in->n_rows;
+        *pending = p.release();
+        return OVTK_OK;
+    }
+    if (int rc = start_wordpiece_encode(h, whitespace, delimiters, in, unk_token_id, &p->out, OVTK_MEM_DEVICE, stream, p->run, &d, p->dense_width))
+        return rc;
+    *pending = p.release();
+    return OVTK_OK;
 }
 
 void ovtk_wordpiece_destroy(ovtk_wordpiece* h) { delete h; }

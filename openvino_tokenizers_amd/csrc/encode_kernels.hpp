@@ -1478,6 +1478,117 @@ static __global__ __launch_bounds__(kBlockThreads) void row_width_kernel(int n_r
         if ((long long)T * n_rows > d.capacity) atomicOr(&w.status->flags, kFlagOutCapacity);
     }
 }
+// PairDenseSink: the tail of the paired graph in the encode's last pass (ovtk_encode_pair_dense_*; the reference's add_second_input,
+// python/openvino_tokenizers/tokenizer_transformations.py:22-304).  The encode runs on 2n rows: rows 0..n-1 are the first sequences,
+// rows n..2n-1 the second ones.  Dense row i = front constants | row i cut | between constants | row n + i cut | behind constants:
+// Truncate with two inputs (src/truncate.cpp:69-144) -> CombineSegments with five segments and their type ids
+// (src/combine_segments.cpp:36-134) -> RaggedToDense three times (src/ragged_to_dense.cpp:70-174): input_ids, attention_mask and
+// token_type_ids [n, T].  T = RunStatus::width (pair_width_kernel, launched in front).
+// No cell has two writers: id() writes a row's own kept ids and nothing else (the wave of row n + i the second sequence's cells of
+// dense row i); row_done() of row i < n writes every other cell of dense row i -- padding, the three constant slots, the whole mask row
+// and the whole type-id row -- and row_done() of the rows >= n writes nothing.  Where a row's partner ends follows from the partner's
+// id count alone (row_cnt: final before this kernel is launched -- pair_width_kernel has read it).
+struct PairDenseSink {
+    int32_t* ids;            // [n * T]
+    uint8_t* mask;           // [n * T] or nullptr
+    int32_t* types;          // [n * T] or nullptr
+    int64_t capacity;        // cells
+    const int32_t* row_cnt;  // EncodeWork::row_cnt of the 2n rows (set at launch)
+    int32_t n;               // pairs (set at launch)
+    int32_t max_length;      // Truncate: ids of a pair that stay
+    int32_t trunc_left;      // 0: the first ids stay, 1: the last
+    int32_t mode;            // 0 only_first, 1 only_second, 2 longest_first
+    int32_t pad_right, pad_value, type_pad;
+    int32_t target_dim;      // < 0: the longest combined row
+    int32_t n_front, n_between, n_behind;
+    int32_t front[kDenseAffix], between[kDenseAffix], behind[kDenseAffix];
+    int32_t type_ids[5];     // front, first, between, second, behind
+    int32_t T;               // (set by start)
+    __device__ __forceinline__ void start(const RunStatus* st) { T = st->width; }
+    // (constant subscripts only, as in DenseSink: the struct stays out of scratch memory)
+    __device__ __forceinline__ int32_t front_at(int k) const { return k == 0 ? front[0] : (k == 1 ? front[1] : (k == 2 ? front[2] : front[3])); }
+    __device__ __forceinline__ int32_t between_at(int k) const { return k == 0 ? between[0] : (k == 1 ? between[1] : (k == 2 ? between[2] : between[3])); }
+    __device__ __forceinline__ int32_t behind_at(int k) const { return k == 0 ? behind[0] : (k == 1 ? behind[1] : (k == 2 ? behind[2] : behind[3])); }
+    // What stays of a pair with fl and sl ids: truncate.cpp:82-143, the arithmetic of tail_segment (ops_kernels.hpp) -- on a tie over an
+    // odd max_length `fl >= sl` gives the odd id to the first sequence.
+    __device__ __forceinline__ void kept(int32_t fl, int32_t sl, int32_t& keep_f, int32_t& keep_s) const {
+        const int32_t m = max_length;
+        keep_f = fl;
+        keep_s = sl;
+        if (fl + sl > m) {
+            const int32_t half = m / 2, half_up = m / 2 + m % 2;
+            if (mode == 0) keep_f = fl > m ? m : fl;
+            else if (mode == 1) keep_s = sl > m ? m : sl;
+            else if (fl >= half_up && sl <= half) keep_f = m - sl;
+            else if (fl < half_up && sl > half) keep_s = m - fl;
+            else {
+                keep_f = half + (m % 2) * (fl >= sl);
+                keep_s = half + (m % 2) * (fl < sl);
+            }
+        }
+    }
+    __device__ __forceinline__ int col0_of(int len) const { return pad_right ? 0 : (T > len ? T - len : 0); }
+    __device__ __forceinline__ void row(int, int, int) const {}
+    __device__ __forceinline__ void id(int r, int cnt, int j, int, int32_t v) const {
+        const bool second = r >= n;
+        const int i = second ? r - n : r;
+        const int32_t other = row_cnt[second ? i : r + n];
+        int32_t kf, ks;
+        kept(second ? other : cnt, second ? cnt : other, kf, ks);
+        const int keep = second ? ks : kf, first = trunc_left ? cnt - keep : 0;
+        if (j < first || j >= first + keep) return;
+        const int len = n_front + kf + n_between + ks + n_behind;
+        const int col = col0_of(len) + n_front + (second ? kf + n_between : 0) + (j - first);
+        if (col < T) ids[(long long)i * T + col] = v;   // (a target_dim below a row's length cuts the row, as RaggedToDense does: :120-135)
+    }
+    __device__ __forceinline__ void row_done(int r, int cnt) const {   // every lane: the cells that are not a row's own ids
+        if (r >= n) return;
+        int32_t kf, ks;
+        kept(cnt, row_cnt[r + n], kf, ks);
+        const int a1 = n_front, a2 = a1 + kf, a3 = a2 + n_between, a4 = a3 + ks, len = a4 + n_behind;
+        const int col0 = col0_of(len);
+        for (int c = lane_id(); c < T; c += kWave) {
+            const int k = c - col0;
+            const bool inside = k >= 0 && k < len;
+            const long long at = (long long)r * T + c;
+            if (mask) mask[at] = inside ? uint8_t(1) : uint8_t(0);
+            if (types)
+                types[at] = !inside ? type_pad
+                                    : (k < a1 ? type_ids[0] : (k < a2 ? type_ids[1] : (k < a3 ? type_ids[2] : (k < a4 ? type_ids[3] : type_ids[4]))));
+            if (!inside) ids[at] = pad_value;
+            else if (k < a1) ids[at] = front_at(k);
+            else if (k >= a2 && k < a3) ids[at] = between_at(k - a2);
+            else if (k >= a4) ids[at] = behind_at(k - a4);
+        }
+    }
+    __device__ __forceinline__ void finish(int, const RunStatus*) const {}
+};
+// T of the paired dense outputs: target_dim, or the longest combined row after the two-input Truncate and the constant segments; more
+// cells than the caller has room for: kFlagOutCapacity (compact_kernel then writes nothing).  n_rows = 2n, the encode's rows.
+static __global__ __launch_bounds__(kBlockThreads) void pair_width_kernel(int n_rows, EncodeWork w, PairDenseSink d) {
+    const int n = n_rows / 2;
+    int m = 0;
+    if (d.target_dim < 0) {
+        for (int r = int(blockIdx.x) * kBlockThreads + int(threadIdx.x); r < n; r += int(gridDim.x) * kBlockThreads) {
+            int32_t kf, ks;
+            d.kept(w.row_cnt[r], w.row_cnt[r + n], kf, ks);
+            const int len = d.n_front + kf + d.n_between + ks + d.n_behind;
+            m = len > m ? len : m;
+        }
+        m = wave_max(m);
+        if (lane_id() == 0 && m > 0) atomicMax(&w.status->width, m);
+    } else if (blockIdx.x == 0 && threadIdx.x == 0) {
+        w.status->width = d.target_dim;
+    }
+    // the last block to arrive checks the room
+    if (!last_block_done(&w.status->width_ticket, gridDim.x, false)) return;
+    if (threadIdx.x == 0) {
+        const int T = __hip_atomic_load(&w.status->width, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((long long)T * n > d.capacity) atomicOr(&w.status->flags, kFlagOutCapacity);
+    }
+}
+template <class Sink>
+struct is_dense_sink { static constexpr bool value = std::is_same<Sink, DenseSink>::value || std::is_same<Sink, PairDenseSink>::value; };
 struct WireSink {
     int32_t* hdr;      // i32 n_ids, i32 n_rows, 0, 0
     int32_t* ends;     // [max_rows]
@@ -1663,7 +1774,7 @@ __device__ __forceinline__ void compact_body(int n_rows, const EncodeWork& w, Si
         const int sv = have ? w.row_stage[rj] : 0;
         const int uv = have ? w.row_used[rj] : 0;
         long long toff;
-        if constexpr (std::is_same<Sink, DenseSink>::value) {
+        if constexpr (is_dense_sink<Sink>::value) {
             toff = 0;   // (a dense cell's place follows from its row and column alone)
         } else if (w.tile_sums && !solo) {
             // the tile's offset = the counts of the tiles in front of it, summed here (tile_cnt: 4 bytes per 64 rows, hot in every L2;

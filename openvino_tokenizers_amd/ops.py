@@ -1822,3 +1822,8 @@ class FusedSplitWordpiece:
             L.check(lib, lib.ovtk_encode_finish(pending, C.byref(out)))
             return [ob[:out.n_rows], oe[:out.n_rows], ids[:out.n_data]]
         return ticket
+
+
+# The paired one-call encodes (ops.FusedPairEncodeDense, ops.FusedPairWordpieceDense) are defined in pair_ops.py.  This import must stay
+# the LAST statement of this module: pair_ops imports _host, _Mem and _ragged_in from here, which exist only once everything above has run.
+from .pair_ops import TRUNC_MODES, FusedPairEncodeDense, FusedPairWordpieceDense  # noqa: E402,F401

@@ -14,6 +14,10 @@ through the C ABI, one library call per node -- what `core.add_extension()` + th
   RegexSplit(\\s+, remove) RegexSplit(BERT delimiters, isolate) WordpieceTokenizer
                                                                 -> FusedSplitWordpieceStep    ovtk_wordpiece_encode_run
   Truncate CombineSegments Padding                              -> FusedEncodeTailStep        ovtk_encode_tail_run
+  [SpecialTokensSplit] RegexSplit BPETokenizer PairTruncation PairCombineSegments PairPadding (a list made by add_second_input)
+                                                                -> FusedPairEncodeDenseStep   ovtk_encode_pair_dense_enqueue / _finish
+  the BERT splits WordpieceTokenizer PairTruncation PairCombineSegments PairPadding
+                                                                -> FusedPairWordpieceDenseStep ovtk_wordpiece_encode_pair_dense_enqueue
   VocabDecoder [ByteFallback] FuzeRagged                        -> FusedDetokenizeStep        ovtk_detokenize_run
 
 and leaves every other step as it is -- a RegexSplit / BPETokenizer pair with a BytesToCharsStep between them and a VocabDecoder with a
@@ -530,6 +534,206 @@ class FusedDetokenizeStep(Step):
         return "text", self.op.evaluate([vals[0]] + self.dec.vocab)
 
 
+# ---------------------------------------------------------------------------------------------------------------- paired input
+# The mirror of the reference's add_second_input (python/openvino_tokenizers/tokenizer_transformations.py:22-304).  Pipeline.run_pair
+# concatenates the two string inputs and runs the front steps on all nA + nB rows; the pair steps below get the state
+# ("pair_ids", [first begins, first ends, second begins, second ends, ids, second_empty]): the halves of the ragged ids, broadcast 1
+# against n, over one ids tensor.  second_empty: the second input had no row -- its begins / ends are zeros, the constants the pair
+# signature adds have length 0, max_length stays reduced (:103-120, :196-200).
+def _signature_slots(pair_ids):
+    """front / between / behind constants of a pair signature, and the positions of its two sequence entries."""
+    seq = [k for k, v in enumerate(pair_ids) if v <= -1]
+    return list(pair_ids[:seq[0]]), list(pair_ids[seq[0] + 1:seq[1]]), list(pair_ids[seq[1] + 1:]), seq
+
+
+class PairTruncationStep(Step):
+    """src/truncate.cpp:69-144, two inputs.  max_length: what Truncate receives (add_second_input has subtracted the added tokens)."""
+    pair = True
+
+    def __init__(self, max_length, side="right", mode="longest_first", lib=None):
+        self.max_length, self.side, self.mode, self.op = int(max_length), side, mode, K.Truncate(lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "pair_ids"
+        fb, fe, sb, se, ids, second_empty = vals
+        out = self.op.evaluate([fb, fe, ids, sb, se, ids, np.int32(self.max_length), self.side.encode(), self.mode.encode()])
+        return "pair_ids", [out[0], out[1], out[3], out[4], ids, second_empty]
+
+
+class PairCombineSegmentsStep(Step):
+    """src/combine_segments.cpp:36-134 over a pair signature: a non-negative entry is one constant id, an entry <= -1 a sequence (the
+    first such entry the first input); type_ids: one per entry; n_single: the entries the single signature had (the rest were added:
+    their constants have length 0 when the second input is empty)."""
+    pair = True
+
+    def __init__(self, pair_ids, type_ids, n_single, lib=None):
+        self.pair_ids, self.type_ids, self.n_single = [int(x) for x in pair_ids], [int(x) for x in type_ids], int(n_single)
+        self.op = K.CombineSegments(lib=lib)
+
+    def segments(self, vals):
+        """-> [(begins, ends, data)] per entry and the indices of the two sequences."""
+        fb, fe, sb, se, ids, second_empty = vals
+        segs, seq = [], []
+        for k, v in enumerate(self.pair_ids):
+            if v <= -1:
+                seq.append(k)
+                segs.append((fb, fe, ids) if len(seq) == 1 else (sb, se, ids))
+            else:
+                segs.append((_like(ids, [0]), _like(ids, [0 if second_empty and k >= self.n_single else 1]), _like(ids, [v])))
+        return segs, seq
+
+    def apply(self, kind, vals):
+        assert kind == "pair_ids"
+        segs, _ = self.segments(vals)
+        out = self.op.evaluate([x for s in segs for x in s] + [np.asarray(self.type_ids, np.int32)])
+        return "typed_ids", [out[0], out[1], out[2], out[5]]
+
+
+class PairPaddingStep(Step):
+    """src/ragged_to_dense.cpp:70-174 three times: input_ids, attention_mask and token_type_ids."""
+    pair = True
+
+    def __init__(self, pad_value=0, type_pad_value=0, pad_right=True, target_dim=None, lib=None):
+        self.pad_value, self.type_pad_value, self.pad_right, self.target_dim = int(pad_value), int(type_pad_value), bool(pad_right), target_dim
+        self.op = K.RaggedToDense(pad_right=pad_right, lib=lib)
+
+    def apply(self, kind, vals):
+        assert kind == "typed_ids"
+        b, e, ids, types = vals
+        lens = e - b
+        width = int(self.target_dim) if self.target_dim is not None else (int(lens.max()) if len(lens) else 0)
+        dense, mask = self.op.evaluate([b, e, ids, np.int32(width), np.int32(self.pad_value)])
+        tdense, _ = self.op.evaluate([b, e, types, np.int32(width), np.int32(self.type_pad_value)])
+        return "dense", [dense, mask, tdense]
+
+
+def add_second_input(steps, single_ids, pair_ids, pair_type_ids, trunc_mode="longest_first", type_pad_value=0):
+    """The step list for paired input (the mirror of tokenizer_transformations.py:22-304); returns a new list, `steps` is untouched.
+    single_ids / pair_ids: the post-processor's signatures in the reference's form -- [101, -1, 102] widened to [101, -1, 102, -2, 102]
+    with pair_type_ids [0, 0, 0, 1, 1].  The checks of assert_and_get_postprocessor and run_on_model, each a ValueError."""
+    single_ids, pair_ids, pair_type_ids = [int(x) for x in single_ids], [int(x) for x in pair_ids], [int(x) for x in pair_type_ids]
+    if pair_ids[:len(single_ids)] != single_ids:
+        raise ValueError("add_second_input: the pair signature must widen the single one")
+    if sum(v <= -1 for v in pair_ids) != 2:
+        raise ValueError("add_second_input: the pair signature must have exactly two sequence entries")
+    if sum(v <= -1 for v in single_ids) != 1:
+        raise ValueError("add_second_input: the single signature must have exactly one sequence entry")
+    if len(pair_type_ids) != len(pair_ids):
+        raise ValueError("add_second_input: one type id per entry of the pair signature")
+    at = next((k for k, s in enumerate(steps) if isinstance(s, CombineSegmentsStep)), None)
+    if at is None or at == 0 or not isinstance(steps[at - 1], TruncationStep):
+        raise ValueError("add_second_input: a TruncationStep in front of the CombineSegmentsStep is needed")
+    comb, trunc = steps[at], steps[at - 1]
+    if comb.prefix + [-1] + comb.suffix != single_ids:
+        raise ValueError("add_second_input: the single signature does not match the CombineSegmentsStep")
+    lib = comb.op._lib
+    num_added_tokens = len(pair_ids) - len(single_ids) - 1   # (:138-151)
+    out = list(steps[:at - 1])
+    out.append(PairTruncationStep(trunc.max_length - num_added_tokens, trunc.side, trunc_mode, lib=lib))
+    out.append(PairCombineSegmentsStep(pair_ids, pair_type_ids, len(single_ids), lib=lib))
+    for s in steps[at + 1:]:
+        if isinstance(s, PaddingStep):
+            s = PairPaddingStep(s.pad_value, type_pad_value, s.pad_right, s.target_dim, lib=lib)
+        out.append(s)
+    return out
+
+
+def _pair_halves(b, e, ids, n_first, n_second):
+    """The ragged ids of the nA + nB rows -> the pair state: the halves, broadcast 1 against n; any other mismatch raises."""
+    if n_second and n_first != n_second and 1 not in (n_first, n_second):
+        raise ValueError(f"run_pair: {n_first} first rows against {n_second} second ones (equal counts, or 1 against n)")
+    rows = max(n_first, n_second)
+    rep = (lambda x, k: x.repeat(k)) if _is_torch(b) else (lambda x, k: np.repeat(x, k))
+    fb, fe = b[:n_first], e[:n_first]
+    if n_first == 1 and rows > 1:
+        fb, fe = rep(fb, rows), rep(fe, rows)
+    if n_second == 0:   # (:116-120: zeroed)
+        sb = se = _like(ids, np.zeros(rows, np.int32))
+    else:
+        sb, se = b[n_first:n_first + n_second], e[n_first:n_first + n_second]
+        if n_second == 1 and rows > 1:
+            sb, se = rep(sb, rows), rep(se, rows)
+    return [fb, fe, sb, se, ids, n_second == 0]
+
+
+class _FusedPairStep(Step):
+    """front of the graph + PairTruncation + PairCombineSegments + PairPadding.  Device tensors with nA == nB: the one call
+    (self.op); broadcast, an empty second input and host arrays: the two-call form -- the fused encode on all rows (self.encode), then
+    ovtk_encode_tail_run over the halves (as FusedEncodeDenseStep.host_form)."""
+    pair = True
+    two_call = False   # True: the two-call form whatever the inputs are (tools/ops_timing.py --only-pair times it beside the one call)
+
+    def _init_tail(self, trunc, comb, pad, lib):
+        self.trunc, self.comb, self.pad, self.lib = trunc, comb, pad, lib
+        front, between, behind, _ = _signature_slots(comb.pair_ids)
+        seq = [k for k, v in enumerate(comb.pair_ids) if v <= -1]
+        t = comb.type_ids
+        self.tail_args = dict(max_length=trunc.max_length, trunc_side=trunc.side, trunc_mode=trunc.mode, pad_right=pad.pad_right, pad_value=pad.pad_value,
+                              type_pad_value=pad.type_pad_value, front=front, between=between, behind=behind,
+                              type_ids=[t[0] if front else 0, t[seq[0]], t[seq[0] + 1] if between else 0, t[seq[1]], t[seq[1] + 1] if behind else 0])
+        self.tail = K.FusedEncodeTail(trunc.max_length, trunc.side, trunc.mode, pad.pad_right, lib=lib)
+
+    def one_call(self, vals, n_first):
+        raise NotImplementedError
+
+    def apply_pair(self, vals, n_first, n_second):
+        device = _is_torch(vals[4]) or hasattr(self.lib, "ovtk_emulator_build")
+        if device and n_first == n_second and not self.two_call:
+            return "dense", self.one_call(vals, n_first)
+        _, (b, e, ids) = self.encode.apply("strings", vals)
+        if len(b) != n_first + n_second:   # (no text at all: the ragged tensor's one-row quirk, regex_split.cpp:129-143 -- every row is empty)
+            b = e = _like(ids, np.zeros(n_first + n_second, np.int32))
+        state = _pair_halves(b, e, ids, n_first, n_second)
+        segs, seq = self.comb.segments(state)
+        return "dense", self.tail.evaluate(segs, self.comb.type_ids, truncated=tuple(seq), pad_value=self.pad.pad_value,
+                                           type_pad_value=self.pad.type_pad_value, target_dim=self.pad.target_dim)
+
+
+class FusedPairEncodeDenseStep(_FusedPairStep):
+    """[SpecialTokensSplit] RegexSplit BPETokenizer + the pair tail: ovtk_encode_pair_dense_enqueue / _finish."""
+
+    def __init__(self, special, split, bpe, trunc, comb, pad):
+        self.special, self.split, self.bpe = special, split, bpe
+        self._init_tail(trunc, comb, pad, bpe.op._lib)
+        self.encode = FusedSplitBPEStep(special, split, bpe)
+        self.op = K.FusedPairEncodeDense(split.op, bpe.op, special.op if special is not None else None, **self.tail_args)
+
+    def one_call(self, vals, n_first):
+        ins = list(vals[:5]) + ([vals[5]] if vals[5] is not None else [])
+        return self.op.evaluate(ins, n_first, _u8(self.split.pattern), self.bpe.consts,
+                                special_pattern=self.special.pattern if self.special is not None else None, target_dim=self.pad.target_dim)
+
+
+class FusedPairWordpieceDenseStep(_FusedPairStep):
+    """The BERT split + WordpieceTokenizer + the pair tail: ovtk_wordpiece_encode_pair_dense_enqueue / ovtk_encode_pair_dense_finish."""
+
+    def __init__(self, ws, pu, wp, trunc, comb, pad):
+        self.ws, self.pu, self.wp = ws, pu, wp
+        self._init_tail(trunc, comb, pad, wp.op._lib)
+        self.encode = FusedSplitWordpieceStep(ws, pu, wp)
+        self.op = K.FusedPairWordpieceDense(ws.op, pu.op, wp.op, **self.tail_args)
+
+    def one_call(self, vals, n_first):
+        return self.op.evaluate(list(vals[:5]), n_first, _u8(self.ws.pattern), _u8(self.pu.pattern), self.wp.consts, target_dim=self.pad.target_dim)
+
+
+def _pair_tail(steps, i):
+    """PairTruncation PairCombineSegments PairPadding at steps[i:] that the one call covers (at most four constants in a slot, one type id
+    per slot) -> the three steps or None."""
+    if i + 2 >= len(steps) or not (isinstance(steps[i], PairTruncationStep) and isinstance(steps[i + 1], PairCombineSegmentsStep) and
+                                   isinstance(steps[i + 2], PairPaddingStep)):
+        return None
+    comb = steps[i + 1]
+    front, between, behind, seq = _signature_slots(comb.pair_ids)
+    if max(len(front), len(between), len(behind)) > 4 or seq[0] >= comb.n_single or seq[1] < comb.n_single:
+        return None
+    t = comb.type_ids
+    for lo, hi in ((0, seq[0]), (seq[0] + 1, seq[1]), (seq[1] + 1, len(t))):
+        if len(set(t[lo:hi])) > 1:
+            return None
+    return steps[i], comb, steps[i + 2]
+
+
 # ---------------------------------------------------------------------------------------------------------------- the rewrite
 def _span_pattern(step):
     """A split the fused encode has a scanner for (api_encode.cpp ovtk_regex_split_create: pattern equality picks it): isolate, no invert, no
@@ -575,6 +779,11 @@ def fuse(steps):
             special, j = s, j + 1
         if j + 1 < n and isinstance(steps[j], RegexSplitStep) and isinstance(steps[j + 1], BPETokenizationStep) and _span_pattern(steps[j]):
             split, bpe = steps[j], steps[j + 1]
+            pt = _pair_tail(steps, j + 2)
+            if pt is not None:
+                out.append(FusedPairEncodeDenseStep(special, split, bpe, *pt))
+                i = j + 5
+                continue
             t = _tail(steps, j + 2)
             if t is not None:
                 out.append(FusedEncodeDenseStep(special, split, bpe, *t[:3]))
@@ -585,6 +794,11 @@ def fuse(steps):
             continue
         # ---- the BERT pre-tokenizer + WordPiece
         if i + 2 < n and _is_bert_split(steps[i], steps[i + 1]) and isinstance(steps[i + 2], WordPieceTokenizationStep):
+            pt = _pair_tail(steps, i + 3)
+            if pt is not None:
+                out.append(FusedPairWordpieceDenseStep(steps[i], steps[i + 1], steps[i + 2], *pt))
+                i += 6
+                continue
             out.append(FusedSplitWordpieceStep(steps[i], steps[i + 1], steps[i + 2]))
             i += 3
             continue
@@ -624,4 +838,36 @@ class Pipeline:
         vals = list(values)
         for s in self.steps:
             kind, vals = s.apply(kind, vals)
+        return vals
+
+    def run_pair(self, first, second):
+        """Paired input (a list made by add_second_input): first / second are [begins, ends, chars] each, numpy or torch.  The two inputs
+        are concatenated, the front steps run on the nA + nB rows, the pair steps on the halves (1 against n is broadcast; an empty
+        second input gives what the reference gives).  Returns [input_ids, attention_mask, token_type_ids]."""
+        fb, fe, fc = first
+        sb, se, sc = second
+        n_first, n_second = len(fb), len(sb)
+        if n_second and n_first != n_second and 1 not in (n_first, n_second):
+            raise ValueError(f"run_pair: {n_first} first rows against {n_second} second ones (equal counts, or 1 against n)")
+        if _is_torch(fc):
+            import torch
+            sb, se, sc = (torch.as_tensor(x, device=fc.device) for x in (sb, se, sc))
+            cat = torch.cat
+            rows = torch.arange(n_first + n_second + 1, dtype=torch.int32, device=fc.device)
+        else:
+            sb, se, sc = (np.asarray(x.cpu() if _is_torch(x) else x) for x in (sb, se, sc))
+            cat = np.concatenate
+            rows = np.arange(n_first + n_second + 1, dtype=np.int32)
+        off = len(fc)
+        kind, vals = "strings", [rows[:-1], rows[1:], cat([fb, sb + off]), cat([fe, se + off]), cat([fc, sc]), None]
+        for s in self.steps:
+            if getattr(s, "pair", False) and kind == "strings":
+                kind, vals = s.apply_pair(vals, n_first, n_second)
+            elif getattr(s, "pair", False) and kind == "ids":
+                b, e, ids = vals
+                if len(b) != n_first + n_second:   # (no text at all: the ragged tensor's one-row quirk -- every row is empty)
+                    b = e = _like(ids, np.zeros(n_first + n_second, np.int32))
+                kind, vals = s.apply("pair_ids", _pair_halves(b, e, ids, n_first, n_second))
+            else:
+                kind, vals = s.apply(kind, vals)
         return vals

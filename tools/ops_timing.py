@@ -94,6 +94,76 @@ def sp_model_tables(model):
     return pieces, np.array(scores, np.float32), blob
 
 
+def pair_timing(args):
+    """Paired input (pipeline.add_second_input, tokenizer_transformations.py:22-304): wall time per batch of the one call
+    (ovtk_*_pair_dense_enqueue / _finish), of the two-call form (the fused encode on all rows, then ovtk_encode_tail_run over the halves)
+    and of the op-by-op chain -- the config-3 text (BERT fixture) and the config-2 text (GPT-2 fixture), each split into two halves of
+    rows / 2 rows, in one run.  One JSON line per form; the three must agree bit for bit before anything is timed."""
+    import json
+    import time
+    from openvino_tokenizers_amd import _lib as L
+    from openvino_tokenizers_amd import pipeline as P
+    from tools.harness import BpeTok, pack_strings
+    from tools.make_tokenizers import load_tokenizer
+    from tools.workloads import TextModel
+    if args.emu:
+        lib = L.load(Path(__file__).resolve().parent.parent / "tests" / "emu" / "build" / "libovtk_emu.so")
+        sync, place = (lambda: None), (lambda a: a)
+    else:
+        import torch
+        lib = L.load()
+        sync, place = torch.cuda.synchronize, (lambda a: torch.as_tensor(a, device="cuda:0"))
+    half = args.rows // 2
+    small = "_small" if args.emu else ""
+
+    def halves(lower):   # (config 3: ~256-byte lower-cased rows; config 2: ~--bytes-byte rows)
+        b, e, c = TextModel(1234, "zipf").batch(2 * half, min(256, args.bytes) if lower else args.bytes, seed=1000)
+        if lower:
+            c = np.frombuffer(c.tobytes().lower(), np.uint8).copy()
+        cut = int(e[half - 1])
+        return [place(x) for x in (b[:half], e[:half], c[:cut])], [place(x) for x in (b[half:] - cut, e[half:] - cut, c[cut:])]
+    bert = load_tokenizer("bert" + small)
+    gpt2 = BpeTok.load("gpt2" + small)
+    bert_consts = list(pack_strings(bert["vocab"])) + [np.asarray(bert["unk_id"], np.int32)]
+    cls, sep = bert["vocab"].index(b"[CLS]"), bert["vocab"].index(b"[SEP]")
+    graphs = {
+        "BERT, config-3 text": (True, [P.RegexSplitStep(P.BERT_WS, "remove", lib=lib), P.RegexSplitStep(P.BERT_PUNCT, "isolate", lib=lib),
+                                       P.WordPieceTokenizationStep(bert_consts, bert["suffix_indicator"], bert["max_bytes_per_word"], lib=lib),
+                                       P.TruncationStep(126, "right", lib=lib), P.CombineSegmentsStep([cls], [sep], lib=lib), P.PaddingStep(0, lib=lib)],
+                                [cls, -1, sep], [cls, -1, sep, -2, sep], [0, 0, 0, 1, 1]),
+        "GPT-2, config-2 text": (False, [P.RegexSplitStep(gpt2.pattern, "isolate", lib=lib), P.BPETokenizationStep(gpt2.consts, lib=lib, **gpt2.attrs),
+                                         P.TruncationStep(254, "right", lib=lib), P.CombineSegmentsStep([0], [2], lib=lib), P.PaddingStep(1, lib=lib)],
+                                 [0, -1, 2], [0, -1, 2, 2, -2, 2], [0] * 6),
+    }
+    lines = []
+    for name, (lower, steps, single, pair, types) in graphs.items():
+        first, second = halves(lower)
+        chain = P.Pipeline(P.add_second_input(steps, single, pair, types))
+        one, two = chain.fused(), chain.fused()
+        two.steps[-1].two_call = True
+        forms = {"one call": one, "two calls": two, "op by op": chain}
+        ref = None
+        for form, pipe in forms.items():
+            out = [np.asarray(x.cpu() if hasattr(x, "cpu") else x) for x in pipe.run_pair(first, second)]
+            ref = ref or out
+            assert all(np.array_equal(a, r) for a, r in zip(out, ref)), f"{name}: {form} differs from the one call"
+        for form, pipe in forms.items():
+            times = []
+            for _ in range(args.reps):
+                sync()
+                t0 = time.perf_counter()
+                pipe.run_pair(first, second)
+                sync()
+                times.append(time.perf_counter() - t0)
+            lines.append(dict(graph=name, form=form, pairs=half, bytes_per_row=min(256, args.bytes) if lower else args.bytes, width=int(ref[0].shape[1]), reps=args.reps,
+                              ms_median=round(1e3 * float(np.median(times)), 4), ms_min=round(1e3 * min(times), 4)))
+            print(json.dumps(lines[-1]), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=65536)
@@ -105,11 +175,16 @@ def main():
     ap.add_argument("--only-tf-ops", action="store_true", help="StringToHashBucket, EqualStr, RaggedToRagged beside UTF8Validate and nothing else")
     ap.add_argument("--only-string-ops", action="store_true", help="BytesToChars, CharsToBytes, ContribStringSplit, ContribStringJoin beside UTF8Validate and nothing else")
     ap.add_argument("--only-numeric", action="store_true", help="NumericToString per element type beside UTF8Validate and nothing else")
+    ap.add_argument("--only-pair", action="store_true", help="paired input: the one call beside the two-call form and the op-by-op chain, and nothing else")
+    ap.add_argument("--out", default=None, help="--only-pair: also append the JSON lines to this file")
     ap.add_argument("--numeric-n", type=int, default=8 << 20)
     ap.add_argument("--detok-rows", type=int, default=16384)
     ap.add_argument("--detok-seq", type=int, default=2048)
     ap.add_argument("--emu", action="store_true", help="the SIMT-emulator build on host arrays (a smoke test of this script; the times mean nothing)")
     args = ap.parse_args()
+    if args.only_pair:
+        pair_timing(args)
+        return
     from openvino_tokenizers_amd import _lib as L
     from openvino_tokenizers_amd.ops import (BPETokenizer, CombineSegments, FusedEncodeTail, FusedSplitBPE, RaggedToDense, RegexSplit,
                                              SpecialTokensSplit, StringTensorPack, StringTensorUnpack, TrieTokenizer, Truncate, UTF8Validate)
