@@ -801,9 +801,23 @@ private:
         const long long units = ((long long)n_rows_ + kCompactRows - 1) / kCompactRows * split;
         const int cgrid = int(std::max<long long>(1, std::min<long long>((units + kWavesPerBlock - 1) / kWavesPerBlock, (long long)device_cu_count(device_) * 16)));
         const RaggedSink rsink{d_ids_, d_begins_, d_ends_};
+        // The ragged result of a call whose rows lookup_span_kernel has just staged, a stretch per wave (launch_middle: the same
+        // rows_grid): compact_stretch_kernel, a wave per stretch.  Anything else -- another sink, offsets from tile_off, items shared by
+        // several waves, the short path's second set of launches (the span kernel is not part of it) -- is compact_kernel's.
+        int stretch_rows = 0;
+        if (!dense_on_ && !wire_.hdr && w.tile_sums && split == 1 && plan_.front == kFrontSpan && (w.launch_mask & kLaunchSpan)) {
+            int32_t rows = 0;
+            rows_grid(d_in_.n_rows, grid_, rows);
+            if (rows >= 1 && rows <= kWave) stretch_rows = rows;
+        }
         with_bool(plan_.stage16, [&](auto s16) {
             constexpr bool S16 = decltype(s16)::value;
-            if (pair_on_) {
+            if (stretch_rows) {
+                w.rows_per_wave = stretch_rows;
+                const long long items = ((long long)n_rows_ + stretch_rows - 1) / stretch_rows;
+                const int sgrid = int(std::max<long long>(1, std::min<long long>((items + kWavesPerBlock - 1) / kWavesPerBlock, (long long)device_cu_count(device_) * 16)));
+                OVTK_LAUNCH(ws.marks, "compact", (compact_stretch_kernel<S16>), sgrid, kBlockThreads, s_, n_rows_, w, rsink);
+            } else if (pair_on_) {
                 PairDenseSink pair = pair_;
                 pair.row_cnt = w.row_cnt;
                 pair.n = n_rows_ / 2;

@@ -1394,7 +1394,8 @@ static __global__ __launch_bounds__(kBlockThreads) void count_scan_kernel(int n_
 // serves all of them, and the staged ids of all its rows are requested before the first is stored -- a wave pays a few
 // memory round trips per item instead of three dependent ones per row (the kernel was latency-bound: 30 -> 23 us at config 2).
 // Unused staging entries (rows that had deferred pieces) are squeezed out by ballot compaction.
-constexpr int kCompactRows = 4;    // rows per work item (8: no better)
+constexpr int kCompactRows = 4;    // rows per work item (8: no better for the kernel alone on one stream -- what the three-stream loop pays for is
+                                   // its instructions and wave slots: compact_stretch_kernel below)
 constexpr int kCompactChunks = 3;  // 64-entry chunks of a row held in registers; longer rows finish in a loop
 // Where compact_body puts the result.  RaggedSink: the caller's begins / ends / ids (the ops' contract).  WireSink: the
 // row-shard exchange's wire (ops_kernels.hpp "row-shard exchange": header | i32 ends[max_rows] | pad_ids ids of 2 or 4
@@ -1636,7 +1637,7 @@ struct __attribute__((packed, aligned(1))) FlatBytes8 { uint32_t d[2]; };
 // A stretch of `total_used` staging entries from `stage_bytes` on -> i32 ids at `out`: a widening copy when no entry of it is unused
 // (`plain`), else the valid entries squeezed through `buf` (kFlatIds ids of LDS, the wave's own).  compact_flat's copy, and the tail of
 // lookup_span_kernel's one-pass form (the wave's whole stretch).
-template <bool S16>
+template <bool S16, int U = 2>   // U: the plain form's groups of 4 x 64 entries in flight
 __device__ __forceinline__ void flat_copy(const uint8_t* stage_bytes, int total_used, bool plain, int32_t* out, int32_t* buf, int part, int split) {
     constexpr int E = S16 ? 8 : 4;   // entries per 16 bytes
     const int l = lane_id();
@@ -1655,8 +1656,8 @@ __device__ __forceinline__ void flat_copy(const uint8_t* stage_bytes, int total_
         // round trip per step (rows of 8 KB: 14 steps per item).  A lane takes FOUR entries per load (8 bytes of u16 / 16 bytes of i32) and
         // stores them as 16 bytes: every load and every store of the wave is one contiguous stretch (eight entries per lane and two
         // stores 32 bytes apart were measured first: compact_kernel 19.9 -> 22.6 us).
-        constexpr int U = 2;   // groups of 4 x 64 entries in flight (512 ids a step: config 2's items are ~450; four cost every item the
-                               // address arithmetic of two groups it does not have)
+        // U = 2 for compact_kernel's items (512 ids a step: config 2's items are ~450; four cost every item the address arithmetic of two
+        // groups it does not have)
         for (int off0 = part * (U * kWave * 4); off0 < total_used; off0 += split * (U * kWave * 4)) {
             uint32_t x[U][4];
 #pragma unroll
@@ -1741,6 +1742,87 @@ __device__ __forceinline__ bool compact_flat(const EncodeWork& w, const RaggedSi
     }
     flat_copy<S16>(reinterpret_cast<const uint8_t*>(w.stage) + (long long)base[0] * (S16 ? 2 : 4), total_used, plain, sink.ids + o[0], buf, part, split);
     return true;
+}
+
+// compact_body's steps as functions, for compact_stretch_kernel.  (compact_body keeps its own text: with these calls in it the compiler
+// laid compact_kernel<DenseSink> out ~190 instructions longer, and `bench.py --config pipeline` ran 2.3 % slower.)
+// Nothing to write (every wave of the launch agrees): a flag that ends the attempt, or work left to a kernel that was not launched.
+__device__ __forceinline__ bool compact_nothing_to_write(const EncodeWork& w, uint32_t more_flags) {
+    // kFlagTailPending: merge_kernel's folded tail left the exact pieces and the tile scan to a second attempt -- tile_off
+    // and parts of the staging buffer hold whatever the previous call left there
+    if ((w.status->flags | more_flags) & (kFatalFlags | kFlagOutCapacity | kFlagDeferOverflow | kFlagExactOverflow | kFlagScratchOverflow |
+                                         kFlagTailPending))
+        return true;
+    // the short path: rows or pieces were left to a kernel that was not launched (the host launches it, and this kernel again).
+    // Unresolved pieces = entries of the deferred list: with span_sums nothing else is filed there (a counter of its own, one more add
+    // per flush on ONE address, cost text that misses everywhere half its rate: 135 000 flushes per batch of uniform-random text).
+    if ((w.skip_mask & kSkipPending) && w.status->n_pending != 0) return true;
+    if (w.skip_mask & kSkipMerge) {
+        const int mine = lane_id() < kShards ? __hip_atomic_load(&w.status->shard_count[lane_id() * kCounterStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        if (__ballot(mine != 0)) return true;
+    }
+    return false;
+}
+// The counts of the tiles in front of `tile`, summed by the wave (tile_sums; wave-uniform `tile`).
+// tile_cnt: 4 bytes per 64 rows, hot in every L2; the array has the slack for 16-byte reads.  What merge_kernel's last block did for
+// everybody, at the price of a ticket and a scan on every call's chain.  A lane takes sixteen tiles per step, its loads leave together
+// with the caller's `acc` (values of its own that belong to the sum) -- before anything waits for those.
+// (whole groups of sixteen in front of the tile unmasked -- a lane's group counts or it does not --, the up to fifteen tiles
+// between the last whole group and the tile one to a lane: 22 vector instructions a step where masking every value took 64)
+__device__ __forceinline__ int tiles_in_front(const EncodeWork& w, int tile, int acc = 0) {
+    const int l = lane_id();
+    const int whole = tile >> 4, rest = tile & 15;   // (wave-uniform)
+    for (int g0 = 0; g0 < whole; g0 += kWave) {
+        const int g = g0 + l;
+        int4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = g < whole ? *reinterpret_cast<const int4*>(w.tile_cnt + 16 * g + 4 * u) : int4{0, 0, 0, 0};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc += (v[u].x + v[u].y) + (v[u].z + v[u].w);
+    }
+    acc += l < rest ? w.tile_cnt[16 * whole + l] : 0;
+    return wave_sum(acc);
+}
+// Up to kCompactRows rows, [row0, row_end), a row at a time: a lane per staging entry, the unused ones left out by ballot.
+// (the sink by value: by reference PairDenseSink went to scratch memory, see DenseSink)
+template <class Sink, bool S16>
+__device__ __forceinline__ void compact_rows(const EncodeWork& w, Sink sink, int row0, int row_end, const int (&cnt)[kCompactRows],
+                                             const int (&o)[kCompactRows], const int (&base)[kCompactRows], const int (&used)[kCompactRows]) {
+    const int l = lane_id();
+    int32_t v[kCompactRows][kCompactChunks];
+#pragma unroll
+    for (int q = 0; q < kCompactRows; ++q)
+#pragma unroll
+        for (int k = 0; k < kCompactChunks; ++k)
+            v[q][k] = (k * kWave + l < used[q]) ? stage_get_t<S16>(w, base[q] + k * kWave + l) : kEmptyId;
+#pragma unroll
+    for (int q = 0; q < kCompactRows; ++q) {
+        const int row = row0 + q;
+        if (row >= row_end) break;
+        if (l == 0) sink.row(row, o[q], o[q] + cnt[q]);
+        int run = 0;
+#pragma unroll
+        for (int k = 0; k < kCompactChunks; ++k) {
+            if (k * kWave < used[q]) {
+                const unsigned long long m = __ballot(v[q][k] != kEmptyId);
+                if (v[q][k] != kEmptyId) {
+                    const int j = run + rank_below(m);
+                    sink.id(row, cnt[q], j, o[q] + j, v[q][k]);
+                }
+                run += __popcll(m);
+            }
+        }
+        for (int b = kCompactChunks * kWave; b < used[q]; b += kWave) {
+            const int x = (b + l < used[q]) ? stage_get_t<S16>(w, base[q] + b + l) : kEmptyId;
+            const unsigned long long m = __ballot(x != kEmptyId);
+            if (x != kEmptyId) {
+                const int j = run + rank_below(m);
+                sink.id(row, cnt[q], j, o[q] + j, x);
+            }
+            run += __popcll(m);
+        }
+        sink.row_done(row, cnt[q]);
+    }
 }
 
 template <class Sink, bool S16 = false>
@@ -1856,8 +1938,9 @@ __device__ __forceinline__ void compact_body(int n_rows, const EncodeWork& w, Si
     sink.finish(n_rows, w.status);
 }
 
-template <class Sink, bool S16 = false>
-static __global__ __launch_bounds__(kBlockThreads) void compact_kernel(int n_rows, EncodeWork w, Sink sink) {
+// What the call's last kernel does before it writes anything (every thread of every block calls it: block 0 works, all meet at a
+// barrier).  Returns kFlagOutCapacity as THIS launch found it (block 0, tile_sums), else 0.
+__device__ __forceinline__ uint32_t compact_report(int n_rows, const EncodeWork& w) {
     // The call's last kernel reports: every kernel before it is through (stream order), so the status block holds its final
     // values -- block 0 writes what the host reads (the scalar fields, the shards' deferred counts) straight into the caller's
     // pinned block and zeroes the workspace's other status block for its next call.  Two dispatches less per call (status
@@ -1875,7 +1958,6 @@ static __global__ __launch_bounds__(kBlockThreads) void compact_kernel(int n_row
         uint32_t* nxt = reinterpret_cast<uint32_t*>(w.next_status);
         for (int i = int(threadIdx.x); i < w.status_words; i += kBlockThreads) nxt[i] = 0u;
     }
-    __shared__ int32_t flat_all[std::is_same<Sink, RaggedSink>::value ? kWavesPerBlock * kFlatIds : 1];
     __shared__ uint32_t over_s;   // block 0: kFlagOutCapacity as this launch found it (the block's threads must agree on it)
     if (threadIdx.x == 0) over_s = 0u;
     if (w.tile_sums && blockIdx.x == 0) {
@@ -1905,7 +1987,74 @@ static __global__ __launch_bounds__(kBlockThreads) void compact_kernel(int n_row
         }
     }
     __syncthreads();
-    compact_body<Sink, S16>(n_rows, w, sink, false, std::is_same<Sink, RaggedSink>::value ? flat_all + wave_in_block() * kFlatIds : nullptr, over_s);
+    return over_s;
+}
+
+template <class Sink, bool S16 = false>
+static __global__ __launch_bounds__(kBlockThreads) void compact_kernel(int n_rows, EncodeWork w, Sink sink) {
+    __shared__ int32_t flat_all[std::is_same<Sink, RaggedSink>::value ? kWavesPerBlock * kFlatIds : 1];
+    const uint32_t over = compact_report(n_rows, w);
+    compact_body<Sink, S16>(n_rows, w, sink, false, std::is_same<Sink, RaggedSink>::value ? flat_all + wave_in_block() * kFlatIds : nullptr, over);
+}
+
+// ---- the short path's tail (RaggedSink, tile_sums, one wave per item): the work item is the rows of ONE wave of lookup_span_kernel,
+// [k * R, (k + 1) * R) with R = rows_per_wave.  That wave made one staging reservation for all of them (span_kernel.hpp "staging"), so
+// they are one stretch of the staging buffer and one stretch of the output: what compact_kernel pays per item of kCompactRows rows -- the
+// tile's 64 row records, the sum of the tiles in front, a 64-lane scan, sixteen readlanes -- is paid once per R rows here (config 2:
+// R = 16, 4 096 items instead of 16 384), the rows' begins / ends leave with one store per array, and the copy is one flat_copy over
+// the whole stretch.  A stretch that is not what the records of a span wave's rows look like (a row left to the generic kernel, a gap)
+// goes row by row through compact_rows, as in compact_kernel; so does any batch whose rows were not staged that way, at its price.
+// R: 1..64, any relation to kRowTile -- a stretch may begin inside a tile and end in the next.
+constexpr int kStretchGroups = 4;   // flat_copy's groups of 4 x 64 entries in flight: a stretch of config 2 is ~1 800 ids, two steps of 1 024
+template <bool S16>
+static __global__ __launch_bounds__(kBlockThreads) void compact_stretch_kernel(int n_rows, EncodeWork w, RaggedSink sink) {
+    __shared__ int32_t flat_all[kWavesPerBlock * kFlatIds];
+    const uint32_t over = compact_report(n_rows, w);
+    if (compact_nothing_to_write(w, over)) return;
+    const int l = lane_id();
+    const int R = w.rows_per_wave;
+    const int n_items = (n_rows + R - 1) / R;
+    const int n_waves = int(gridDim.x) * kWavesPerBlock;
+    int32_t* const buf = flat_all + wave_in_block() * kFlatIds;
+    for (int item = int(blockIdx.x) * kWavesPerBlock + wave_in_block(); item < n_items; item += n_waves) {
+        const int row0 = item * R;
+        const int nr = n_rows - row0 < R ? n_rows - row0 : R;
+        const int tile = row0 / kRowTile, in_front = row0 % kRowTile;   // (wave-uniform) rows of my first row's tile in front of it
+        // lane i = row row0 + i; the rows of the tile in front of the stretch, a lane each, leave with them and with the tile sums
+        const bool mine = l < nr;
+        const int c = mine ? w.row_cnt[row0 + l] : 0;
+        const int sv = mine ? w.row_stage[row0 + l] : 0;
+        const int uv = mine ? w.row_used[row0 + l] : 0;
+        const int toff = tiles_in_front(w, tile, l < in_front ? w.row_cnt[tile * kRowTile + l] : 0);
+        const int incl = wave_incl_sum(c);
+        const int total_cnt = wave_readlane(incl, kWave - 1);
+        // (the total is block 0's to find out while everybody writes -- a stretch that would leave the caller's buffer writes nothing,
+        // the call ends with OVTK_E_CAPACITY either way)
+        if ((long long)toff + total_cnt > w.out_cap) continue;
+        const int o = toff + (incl - c);
+        // one stretch of staging: every row has its entries (none is pending) and begins where the row before it ends
+        const int next_sv = int(lane_next(uint32_t(sv)));
+        const bool flat = __ballot(mine && (uv < 0 || (l + 1 < nr && next_sv != sv + uv))) == 0ull;
+        if (flat) {
+            if (mine) sink.row(row0 + l, o, o + c);
+            const int total_used = wave_sum(uv);
+            flat_copy<S16, kStretchGroups>(reinterpret_cast<const uint8_t*>(w.stage) + (long long)wave_readlane(sv, 0) * (S16 ? 2 : 4), total_used,
+                                           total_used == total_cnt, sink.ids + toff, buf, 0, 1);
+            continue;
+        }
+        for (int q0 = 0; q0 < nr; q0 += kCompactRows) {
+            int cnt[kCompactRows], oo[kCompactRows], base[kCompactRows], used[kCompactRows];
+#pragma unroll
+            for (int q = 0; q < kCompactRows; ++q) {   // (nr <= 64: q0 + q <= 63; lanes behind the stretch hold zeros)
+                const int j = q0 + q;
+                cnt[q] = wave_readlane(c, j);
+                oo[q] = wave_readlane(o, j);
+                base[q] = wave_readlane(sv, j);
+                used[q] = wave_readlane(uv, j);
+            }
+            compact_rows<RaggedSink, S16>(w, sink, row0 + q0, row0 + nr, cnt, oo, base, used);
+        }
+    }
 }
 
 // ---- a small batch in ONE launch (BASELINE config 1: 32 x 128-byte strings; any batch of a few hundred short rows).
