@@ -590,7 +590,7 @@ int ovtk_regex_normalization_run(ovtk_regex_normalization* h, const ovtk_strings
 int64_t ovtk_regex_normalization_bound(ovtk_regex_normalization* h, int64_t n, int64_t n_chars);
 void ovtk_regex_normalization_destroy(ovtk_regex_normalization* h);
 
-/* ---------------------------------------------------------------- SentencepieceTokenizer (unigram models) / RaggedToSparse
+/* ---------------------------------------------------------------- SentencepieceTokenizer (unigram and BPE models) / RaggedToSparse
  * ovtk_sentencepiece_run replaces SentencepieceTokenizer::evaluate, src/sentence_piece.cpp:188-350, in its 4-input form (sp model,
  * begins, ends, chars): per sentence SentencePieceProcessor::Encode with the extra options of :58-73, then the sparse outputs of
  * :331-347.  `model`: a serialized sentencepiece ModelProto, host memory, consumed at create (the reference's lazy init, :193-198);
@@ -601,7 +601,11 @@ void ovtk_regex_normalization_destroy(ovtk_regex_normalization* h);
  * is never a candidate; a run of unknown pieces is one unk id, or -- trainer_spec.byte_fallback -- every unknown piece becomes the id
  * of <0xHH> for each of its bytes; add_bos / add_eos put the model's bos / eos id in front / behind, also around an empty sentence;
  * reverse alone reverses the row.
- * OVTK_E_UNSUPPORTED at create, never an approximation: a model_type other than UNIGRAM, treat_whitespace_as_suffix, USER_DEFINED
+ * A BPE model (trainer_spec.model_type) runs through the same calls, bit-exact with bpe::Model::Encode: one-character symbols, the
+ * adjacent pair whose bytes are a NORMAL piece of the highest score merged first, among equal scores the leftmost; the same
+ * post-processing.  Refused for BPE models: UNUSED pieces, two NORMAL pieces of two or more characters that share one float32 score,
+ * a CONTROL / UNKNOWN / BYTE piece of one character.
+ * OVTK_E_UNSUPPORTED at create, never an approximation: a model_type other than UNIGRAM or BPE, treat_whitespace_as_suffix, USER_DEFINED
  * pieces, a piece longer than 1 023 bytes, 4 194 303 or more pieces, nbest_size other than 0 or 1 (sampling), reverse together with
  * add_bos or add_eos (the outcome depends on the order of the extra options), add_bos / add_eos with a model that has no such piece.
  * out: indices i64 [n][2] = (row, position) in row order, values i32 [n], dense_shape i64 [2] = {rows, longest row}; buffers of

@@ -1,4 +1,4 @@
-// api_sentencepiece.cpp -- C-ABI entry points of SentencepieceTokenizer (unigram models) and RaggedToSparse.  Compiled as HIP (hipcc -x hip).
+// api_sentencepiece.cpp -- C-ABI entry points of SentencepieceTokenizer (unigram and BPE models) and RaggedToSparse.  Compiled as HIP (hipcc -x hip).
 // Reference behaviour replaced: src/sentence_piece.cpp:188-350 (evaluate, 4-input form: SentencePieceProcessor::Encode with the
 // extra options of :58-73, then the sparse outputs of :331-347), src/ragged_to_sparse.cpp:27-47.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,8 @@
 #include "ops_kernels.hpp"
 #include "runtime.hpp"
 #include "sentencepiece_kernels.hpp"
+#include "sp_bpe_kernels.hpp"
+#include "sp_bpe_tables.hpp"
 #include "sp_model.hpp"
 #include "tables.hpp"
 
@@ -29,6 +31,8 @@ struct ovtk_sentencepiece {
     DevBuf root, buckets, scores, types, byte_ids;
     int32_t nbest_size = 0;
     float alpha = 0.0f;   // stored as the reference stores it; only sampling reads it
+    bool bpe = false;     // a BPE model: sp_bpe_kernels.hpp stands where the lattice kernels stand
+    int bpe_cuts = 0;     // ... and its cut rule is proved for this vocabulary (sp_bpe_tables.hpp)
     ~ovtk_sentencepiece() { ovtk_charsmap_destroy(cm); }
 };
 
@@ -69,8 +73,9 @@ int ovtk_sentencepiece_create(const uint8_t* model, int64_t model_len, const ovt
         return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: nbest_size other than 0 or 1 selects SampleEncode, which is random (sentence_piece.cpp:238-241)");
     if (p->reverse && (p->add_bos || p->add_eos))
         return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: reverse together with add_bos / add_eos depends on the order of the extra options (sentence_piece.cpp:58-73)");
-    if (m.model_type != kSpUnigram)
-        return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: only UNIGRAM models run here; BPE, WORD and CHAR models are the follow-up");
+    if (m.model_type != kSpUnigram && m.model_type != kSpBpe)
+        return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: only UNIGRAM and BPE models run here; WORD and CHAR models are the follow-up");
+    const bool bpe = m.model_type == kSpBpe;
     if (m.treat_whitespace_as_suffix) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: treat_whitespace_as_suffix");
     if (int64_t(m.pieces.size()) >= int64_t(kUniUnkCode)) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: more than 4 194 302 pieces");
     // ModelInterface::InitializePieces: one UNKNOWN piece, no empty and no repeated piece; min / max score over the NORMAL ones
@@ -119,6 +124,10 @@ int ovtk_sentencepiece_create(const uint8_t* model, int64_t model_len, const ovt
     const int32_t bos_id = control_id(m.bos_piece), eos_id = control_id(m.eos_piece);
     if (p->add_bos && bos_id < 0) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: add_bos with a model that has no bos piece (sentencepiece raises)");
     if (p->add_eos && eos_id < 0) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: add_eos with a model that has no eos piece (sentencepiece raises)");
+    if (bpe) {
+        std::string refusal;
+        if (!sp_bpe_accepts(m, &refusal)) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: " + refusal);
+    }
     int32_t byte_ids[256];
     for (int v = 0; v < 256; ++v) {
         char name[8];
@@ -131,13 +140,15 @@ int ovtk_sentencepiece_create(const uint8_t* model, int64_t model_len, const ovt
     h->device = p->device;
     h->nbest_size = p->nbest_size;
     h->alpha = p->alpha;
+    h->bpe = bpe;
+    h->bpe_cuts = bpe && sp_bpe_cut_rule_holds(m) ? 1 : 0;
     const ovtk_charsmap_params cp{m.add_dummy_prefix, m.remove_extra_whitespaces, m.escape_whitespaces};
     if (int rc = ovtk_charsmap_create(reinterpret_cast<const uint8_t*>(m.precompiled_charsmap.data()), int64_t(m.precompiled_charsmap.size()), &cp,
                                       p->device, &h->cm))
         return rc;   // (the builder's own refusals, its message)
     TrieHost t;
     for (size_t i = 0; i < m.pieces.size(); ++i)   // (ModelInterface::InitializePieces: the other types go to a map no text is looked up in)
-        if (types[i] == kSpNormal || types[i] == kSpUserDefined || types[i] == kSpUnused)
+        if (types[i] == kSpNormal || (!bpe && (types[i] == kSpUserDefined || types[i] == kSpUnused)))   // (BPE: the candidates' lookup; such models have neither)
             t.add(reinterpret_cast<const uint8_t*>(m.pieces[i].piece.data()), m.pieces[i].piece.size(), int32_t(i));
     TrieBucketsHost tb;
     if (!tb.build(t)) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: the pieces' trie has more than 8 million nodes");
@@ -232,7 +243,7 @@ int ovtk_sentencepiece_run(ovtk_sentencepiece* h, const ovtk_strings* in, ovtk_s
         w.status = st;
         if (cap >= INT32_MAX - 1) return set_error(OVTK_E_UNSUPPORTED, "SentencepieceTokenizer: too much text for one call; split it");
         if (int rc = ws->gen[4].ensure(size_t(cap) * sizeof(int32_t))) return rc;
-        if (int rc = ws->gen[5].ensure(size_t(cap) * sizeof(UniEdgeList))) return rc;
+        if (int rc = ws->gen[5].ensure(size_t(cap) * (h->bpe ? sizeof(SpBpeSym) : sizeof(UniEdgeList)))) return rc;
         if (int rc = ws->gen[6].ensure(size_t(cap) * sizeof(UniNode))) return rc;
         if (int rc = ws->stage.ensure(size_t(cap + 2 * n + 2) * sizeof(int32_t))) return rc;
         w.owner = ws->gen[4].as<int32_t>();
@@ -248,11 +259,19 @@ int ovtk_sentencepiece_run(ovtk_sentencepiece* h, const ovtk_strings* in, ovtk_s
                     ws->tiles.as<long long>(), st, kFlagRange);
         OVTK_LAUNCH(ws->marks, "sp_norm_write", each_wave_kernel<CmRow<true>>, wave_grid, kTileThreads, s, (long long)n,
                     (CmRow<true>{cm, b, e, c, (long long)in->n_chars, nullptr, norm_len, norm_b, norm}), (const RunStatus*)st, kStop);
-        // the lattice over each normalized sentence
-        launch_scan(ws->marks, "sp_stretch", s, n, UniStretch{w}, UniStretchApply{w}, UniStretchFin{st, (long long)cap}, ws->tiles.as<long long>(), st,
-                    kFlagRange | kFlagItemsOverflow);
-        OVTK_LAUNCH(ws->marks, "sp_edges", unigram_edges_kernel, unsigned((cap + kTileThreads - 1) / kTileThreads), kTileThreads, s, w);
-        OVTK_LAUNCH(ws->marks, "sp_relax", sp_relax_kernel, lane_grid, kTileThreads, s, (long long)n, (SpRelax{w, h->sp, row_start, row_len}), st, kStop);
+        if (h->bpe) {
+            // symbols, segments, merges and ids: a wave per normalized sentence (gen[5]: the left-over path's symbol lists)
+            launch_scan(ws->marks, "spbpe_stretch", s, n, SpBpeStretch{w}, SpBpeStretchApply{w}, UniStretchFin{st, (long long)cap}, ws->tiles.as<long long>(),
+                        st, kFlagRange | kFlagItemsOverflow);
+            OVTK_LAUNCH(ws->marks, "spbpe_merge", sp_bpe_kernel, wave_grid, kTileThreads, s, (long long)n,
+                        (SpBpeRow{w, h->sp, ws->gen[5].as<SpBpeSym>(), row_start, row_len, h->bpe_cuts}), st, kStop);
+        } else {
+            // the lattice over each normalized sentence
+            launch_scan(ws->marks, "sp_stretch", s, n, UniStretch{w}, UniStretchApply{w}, UniStretchFin{st, (long long)cap}, ws->tiles.as<long long>(), st,
+                        kFlagRange | kFlagItemsOverflow);
+            OVTK_LAUNCH(ws->marks, "sp_edges", unigram_edges_kernel, unsigned((cap + kTileThreads - 1) / kTileThreads), kTileThreads, s, w);
+            OVTK_LAUNCH(ws->marks, "sp_relax", sp_relax_kernel, lane_grid, kTileThreads, s, (long long)n, (SpRelax{w, h->sp, row_start, row_len}), st, kStop);
+        }
         // the sparse outputs
         launch_scan(ws->marks, "sp_offsets", s, n, FiledLen{row_len}, RowOffsets{row_b, row_e, 0},
                     (SparseFin<int64_t>{st, (long long)std::min<int64_t>(out->capacity, INT32_MAX - 1), (long long)n, kStop, d_shape}),
@@ -269,6 +288,7 @@ int ovtk_sentencepiece_run(ovtk_sentencepiece* h, const ovtk_strings* in, ovtk_s
         if (attempt) return set_error(OVTK_E_HIP, "SentencepieceTokenizer: workspace sizing did not converge");
         cap = ws->host_status->stage_need;
     }
+    if (h->bpe && ws->host_status->n_exact > 0) Profiler::get().count("spbpe_leftover_segments", ws->host_status->n_exact);
     out->n = ws->host_status->n_out;
     if (f & kFlagOutCapacity)
         return set_error(OVTK_E_CAPACITY, "SentencepieceTokenizer: output buffers too small (" + std::to_string(out->n) + " ids, capacity " +

@@ -54,6 +54,11 @@ bool Profiler::lookup(const std::string& name, double* ms, int64_t* n) {
     *n = it->second.second;
     return true;
 }
+void Profiler::count(const std::string& name, int64_t n) {
+    if (!on_) return;
+    std::lock_guard<std::mutex> lk(mu_);
+    acc_[name].second += n;
+}
 std::string Profiler::dump() {
     std::lock_guard<std::mutex> lk(mu_);
     std::string out;

@@ -52,6 +52,7 @@ public:
     void reset();
     bool lookup(const std::string& name, double* ms, int64_t* n);
     std::string dump();
+    void count(const std::string& name, int64_t n);   // a counter among the timings: 0 ms, n "launches" (only while enabled)
     // per call
     struct Mark { const char* name; hipEvent_t a, b; };
     void begin(const char* name, hipStream_t s, std::vector<Mark>& marks);

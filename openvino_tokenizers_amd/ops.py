@@ -1006,7 +1006,7 @@ class RegexNormalization(_Op):
 
 
 class SentencepieceTokenizer(_Op):
-    """Reference: src/sentence_piece.cpp (evaluate :188-350), for unigram models.  Inputs: sp_model u8 (a serialized sentencepiece
+    """Reference: src/sentence_piece.cpp (evaluate :188-350), for unigram and BPE models.  Inputs: sp_model u8 (a serialized sentencepiece
     ModelProto, read at the first evaluate), begins, ends, chars.  Outputs: indices i64 [n, 2], values i32 [n], dense_shape i64 [2].
     Attributes and their defaults as the reference's factory gives them (src/tokenizers_factory.cpp:61-67).  What is refused, and
     why: include/ovtk_amd.h, ovtk_sentencepiece_run."""

@@ -3,7 +3,8 @@ on a config-2-shaped batch (65 536 rows x ~512 bytes of zipf text, a GPT-2 speci
 batch for the ops behind the tokenizer), inputs and outputs in HBM:
 
     SentencepieceTokenizer (a fixture unigram model; beside it CharsMapNormalization followed by UnigramTokenizer on whole rows with the
-    model's charsmap and pieces, the two calls the one call replaces; --only-sentencepiece stops behind these rows),
+    model's charsmap and pieces, the two calls the one call replaces, and the same op on a fixture BPE model, checked against the
+    installed `sentencepiece` package on the first rows; --only-sentencepiece stops behind these rows),
     UTF8Validate (both modes), SpecialTokensSplit (the op: count pass, scan, write pass), RegexSplit (the op), StringTensorPack /
     StringTensorUnpack, TrieTokenizer, UnigramTokenizer, CharsMapNormalization, RegexNormalization, Truncate, CombineSegments, RaggedToDense (in bench.py too: --config r2d), the fused tail
     (ovtk_encode_tail_run: Truncate -> CombineSegments -> RaggedToDense x 2 in one call).
@@ -450,12 +451,27 @@ def main():
     pair_head = [to_np(x) for x in sp_pair()]
     n_ids = int(len(pair_head[2]))
     head_ids = pair_head[2][:int(pair_head[1][k - 1])]
+    bpe_model = np.frombuffer((Path(__file__).resolve().parent.parent / "tests" / "golden" / "spm_bpe_unk.model").read_bytes(), np.uint8)
+    bpe_op = SentencepieceTokenizer(lib=lib)
+    bpe_want = None
+    try:
+        import sentencepiece as spm
+        bpe_sp = spm.SentencePieceProcessor(model_proto=bytes(bpe_model))
+        bpe_want = np.array([x for r in range(k) for x in bpe_sp.encode(bytes(c[b[r]:e[r]]))], np.int32)
+    except ImportError:
+        pass
+
+    def bpe_check(out):
+        return bool(np.array_equal(to_np(out[1])[:len(bpe_want)], bpe_want)) and int(to_np(out[2])[0]) == n
     for trial in range(3):
         timed(f"CharsMapNormalization + UnigramTokenizer (whole rows, spm_unigram_nfkc), round {trial}", sp_pair, 3 * n_c + 32 * n + 4 * n_ids, None,
               "two calls, the normalized text and a host wait in between")
         timed(f"SentencepieceTokenizer(spm_unigram_nfkc), round {trial}", lambda: sp_op.evaluate([sp_model] + d[2:5]), n_c + 8 * n + 20 * n_ids,
               lambda out: same([head_ids], [to_np(out[1])], upto=len(head_ids)) and int(to_np(out[2])[0]) == n,
               f"{n_ids} ids: normalize (count, scan, write) -> edges -> relax -> scan -> sparse writer, one enqueue sequence")
+        # the BPE fixture on the same batch, beside the unigram one (its yardstick); the check: the installed package on the first rows
+        timed(f"SentencepieceTokenizer(spm_bpe_unk, a BPE model), round {trial}", lambda: bpe_op.evaluate([bpe_model] + d[2:5]), n_c + 8 * n + 20 * n_ids,
+              bpe_check if bpe_want is not None else None, "normalize (count, scan, write) -> stretch scan -> merge (a wave per sentence) -> scan -> sparse writer, one enqueue sequence")
     if args.only_sentencepiece:
         return
     # ---- UTF8Validate (src/utf8_validate.cpp:18-143): strings in, strings out
