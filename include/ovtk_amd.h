@@ -612,6 +612,24 @@ void ovtk_regex_normalization_destroy(ovtk_regex_normalization* h);
  * `capacity` ids.  ovtk_sentencepiece_bound(h, n, n_chars) is an upper bound of the ids for any input of n sentences and n_chars
  * bytes; a smaller buffer is fine when the ids fit: OVTK_E_CAPACITY otherwise, out->n = the ids the call needs, nothing written.
  * With OVTK_MEM_DEVICE `indices` must be 16-byte aligned.
+ * ovtk_sentencepiece_create_special makes a handle for the 8-input form (:200-230, :286-329: what convert_sentencepiece_model_tokenizer
+ * builds for BPE models): `tokens` / `token_ids` are the added tokens and their ids, HOST memory, consumed at create; run, bound and
+ * destroy are the same calls.  Per row: the tokens are searched as the reference's pattern searches them -- the tokens in input order
+ * joined by `|`, each quoted, a token of ASCII letters only as `\bTOK|TOK\b`, PCRE2_UTF | PCRE2_UCP (\w = L | N | Mn | Pc, PCRE2
+ * 10.46): the leftmost position at which a token matches, there the first token in list order (not the longest); a duplicated token
+ * keeps its first id.  The text between two matches, where there is any, is encoded on its own -- its own dummy prefix, its own bos
+ * under add_bos --, the token's id follows.  An empty row encodes nothing (no bos).  add_eos appends the model's eos id once per row,
+ * empty rows included; reverse reverses the whole row, eos included; reverse together with add_bos / add_eos runs in this form.
+ * Rows that are not valid UTF-8 are undefined in the reference (pcre2_jit_match does not validate); here, as in
+ * ovtk_special_tokens_split_run: no match begins at a continuation byte, a lead byte takes the continuation bytes that follow it (as
+ * many as it asks for at most), a stray continuation byte or a value above U+10FFFF is no word character.
+ * OVTK_E_UNSUPPORTED at create, on top of everything ovtk_sentencepiece_create refuses: an empty token (`\b|\b` would end every
+ * search), a token that is not valid UTF-8 (the reference's pattern fails to compile and silently matches nothing), more than 4 096
+ * tokens, a token longer than 1 023 bytes, a token with a negative id (the reference would emit it as it is; the slot lists here
+ * mark a part of text by a negative id).  A token index outside tokens->chars is OVTK_E_RANGE.
+ * ovtk_sentencepiece_bound for such a handle: with s = the bytes of the shortest token a batch holds at most k = n_chars / s matches
+ * (an id each) and k + n parts, each normalized by itself and given a bos, and an eos per row:
+ * ovtk_charsmap_bound(k + n, n_chars) + (k + n) + k + n.
  * ovtk_ragged_to_sparse replaces RaggedToSparse::evaluate, src/ragged_to_sparse.cpp:27-47: out i32 [n][2] = (row, position) for
  * every element of every row, *n_out = the sum of the rows' lengths (the reference sizes its output ends[last] - begins[0], the same
  * number where the rows are back to back); a row that ends before it begins is OVTK_E_RANGE.  Stateless. */
@@ -632,6 +650,8 @@ typedef struct ovtk_sparse_i32_out {
     int64_t n; /* out: ids written (OVTK_E_CAPACITY: ids needed) */
 } ovtk_sparse_i32_out;
 int ovtk_sentencepiece_create(const uint8_t* model, int64_t model_len, const ovtk_sentencepiece_params* params, ovtk_sentencepiece** out);
+int ovtk_sentencepiece_create_special(const uint8_t* model, int64_t model_len, const ovtk_sentencepiece_params* params, const ovtk_strings* tokens,
+                                      const int32_t* token_ids, ovtk_sentencepiece** out);
 int ovtk_sentencepiece_run(ovtk_sentencepiece* h, const ovtk_strings* in, ovtk_sparse_i32_out* out, int mem, void* stream);
 int64_t ovtk_sentencepiece_bound(ovtk_sentencepiece* h, int64_t n, int64_t n_chars);
 void ovtk_sentencepiece_destroy(ovtk_sentencepiece* h);

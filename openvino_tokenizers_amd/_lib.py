@@ -144,7 +144,7 @@ EXPORTS = [
     "ovtk_unigram_create", "ovtk_unigram_run", "ovtk_unigram_destroy",
     "ovtk_charsmap_create", "ovtk_charsmap_run", "ovtk_charsmap_bound", "ovtk_charsmap_destroy", "ovtk_case_fold_ascii",
     "ovtk_regex_normalization_create", "ovtk_regex_normalization_run", "ovtk_regex_normalization_bound", "ovtk_regex_normalization_destroy",
-    "ovtk_sentencepiece_create", "ovtk_sentencepiece_run", "ovtk_sentencepiece_bound", "ovtk_sentencepiece_destroy", "ovtk_ragged_to_sparse",
+    "ovtk_sentencepiece_create", "ovtk_sentencepiece_create_special", "ovtk_sentencepiece_run", "ovtk_sentencepiece_bound", "ovtk_sentencepiece_destroy", "ovtk_ragged_to_sparse",
     "ovtk_sp_detokenizer_create", "ovtk_sp_detokenizer_run", "ovtk_sp_detokenizer_bound", "ovtk_sp_detokenizer_destroy",
     "ovtk_sp_detokenizer_enqueue", "ovtk_sp_detokenizer_finish",
     "ovtk_string_to_hash_bucket", "ovtk_equal_str", "ovtk_ragged_to_ragged",
@@ -198,6 +198,8 @@ def load(path: os.PathLike | str | None = None) -> C.CDLL:
     lib.ovtk_charsmap_destroy.argtypes = [C.c_void_p]
     lib.ovtk_charsmap_destroy.restype = None
     lib.ovtk_sentencepiece_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(SentencepieceParams), C.POINTER(C.c_void_p)]
+    lib.ovtk_sentencepiece_create_special.argtypes = [C.c_void_p, C.c_int64, C.POINTER(SentencepieceParams), C.POINTER(Strings), C.c_void_p,
+                                                      C.POINTER(C.c_void_p)]
     lib.ovtk_sentencepiece_run.argtypes = [C.c_void_p, C.POINTER(Strings), C.POINTER(SparseI32Out), C.c_int, C.c_void_p]
     lib.ovtk_sentencepiece_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
     lib.ovtk_sentencepiece_bound.restype = C.c_int64

@@ -1007,12 +1007,17 @@ class RegexNormalization(_Op):
 
 class SentencepieceTokenizer(_Op):
     """Reference: src/sentence_piece.cpp (evaluate :188-350), for unigram and BPE models.  Inputs: sp_model u8 (a serialized sentencepiece
-    ModelProto, read at the first evaluate), begins, ends, chars.  Outputs: indices i64 [n, 2], values i32 [n], dense_shape i64 [2].
+    ModelProto, read at the first evaluate), begins, ends, chars -- and, the 8-input form (:200-230, :286-329), the added tokens as
+    tok_begins, tok_ends, tok_chars and their ids i32 (host values, read at the first evaluate): they are cut out of every row and
+    stand as their ids between the parts, each part encoded on its own.  The 8-input form is taken by an op made with
+    special_tokens=True; an op made without it answers 8 inputs with E_UNSUPPORTED, as every op did before the form was built.
+    Outputs: indices i64 [n, 2], values i32 [n], dense_shape i64 [2].
     Attributes and their defaults as the reference's factory gives them (src/tokenizers_factory.cpp:61-67).  What is refused, and
     why: include/ovtk_amd.h, ovtk_sentencepiece_run."""
 
-    def __init__(self, nbest_size=0, alpha=0.0, add_bos=False, add_eos=False, reverse=False, device=0, lib=None):
+    def __init__(self, nbest_size=0, alpha=0.0, add_bos=False, add_eos=False, reverse=False, device=0, lib=None, special_tokens=False):
         super().__init__(device, lib)
+        self.special_tokens = bool(special_tokens)
         self.nbest_size, self.alpha = int(nbest_size), float(alpha)
         self.add_bos, self.add_eos, self.reverse = bool(add_bos), bool(add_eos), bool(reverse)
 
@@ -1021,13 +1026,27 @@ class SentencepieceTokenizer(_Op):
             self._lib.ovtk_sentencepiece_destroy(self._h)
             self._h = None
 
-    def _ensure(self, model):
+    def _ensure(self, model, special=None):
         if self._h:
+            # the model and the added tokens are read once: the handle serves the form it was made for and no other
+            if (special is not None) != self._h_special:
+                raise L.OvtkError(L.E_ARG, "SentencepieceTokenizer: this op's handle was made by a call with "
+                                           f"{8 if self._h_special else 4} inputs; make another op for the other form")
             return
+        self._h_special = special is not None
         buf = np.frombuffer(_bytes_of(model), np.uint8)
+        pbuf = buf.ctypes.data_as(C.c_void_p) if len(buf) else None
         p = L.SentencepieceParams(self.nbest_size, self.alpha, int(self.add_bos), int(self.add_eos), int(self.reverse), self.device)
-        self._chk(self._lib.ovtk_sentencepiece_create(buf.ctypes.data_as(C.c_void_p) if len(buf) else None, C.c_int64(len(buf)), C.byref(p),
-                                                      C.byref(self._h)))
+        if special is None:
+            self._chk(self._lib.ovtk_sentencepiece_create(pbuf, C.c_int64(len(buf)), C.byref(p), C.byref(self._h)))
+            return
+        # the added tokens are constants of the graph: host memory, consumed at create
+        tb, te, tc, ti = (_host(x, dt).reshape(-1) for x, dt in zip(special, (np.int32, np.int32, np.uint8, np.int32)))
+        if len(tb) != len(te) or len(tb) != len(ti):
+            raise L.OvtkError(L.E_ARG, "SentencepieceTokenizer: the special tokens' begins, ends and ids differ in length")
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if len(a) else None   # noqa: E731
+        toks = L.Strings(ptr(tb), ptr(te), ptr(tc), len(tb), len(tc))
+        self._chk(self._lib.ovtk_sentencepiece_create_special(pbuf, C.c_int64(len(buf)), C.byref(p), C.byref(toks), ptr(ti), C.byref(self._h)))
 
     def bound(self, n, n_chars):
         """Ids that n sentences of n_chars bytes can give (ovtk_sentencepiece_bound); the handle must exist (after a first evaluate)."""
@@ -1037,13 +1056,13 @@ class SentencepieceTokenizer(_Op):
         if len(inputs) in (2, 6):   # sentence_piece.cpp:153-157, :257-264: the element::string container stays with the caller
             raise L.OvtkError(L.E_ARG, "SentencepieceTokenizer: string-tensor inputs are a host container; unpack them first "
                                        "(StringTensorUnpack) and pass sp_model, begins, ends, chars")
-        if len(inputs) == 8:
+        if len(inputs) == 8 and not self.special_tokens:
             raise L.OvtkError(L.E_UNSUPPORTED, "SentencepieceTokenizer: the 8-input form (special tokens split off by a regex, "
-                                               "sentence_piece.cpp:200-230, :286-329) is a follow-up; pass sp_model, begins, ends, chars")
-        if len(inputs) != 4:
+                                               "sentence_piece.cpp:200-230, :286-329) is taken by an op made with special_tokens=True")
+        if len(inputs) not in (4, 8):
             raise L.OvtkError(L.E_ARG, "Unexpected input format. SentencepieceTokenizer accepts one string input or three decomposed "
                                        "string inputs (begins, ends, symbols)")   # :162
-        self._ensure(inputs[0])
+        self._ensure(inputs[0], inputs[4:8] if len(inputs) == 8 else None)
         m = _Mem(inputs[3])
         b, pb = m.inp(inputs[1], "i32")
         e, pe = m.inp(inputs[2], "i32")

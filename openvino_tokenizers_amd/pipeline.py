@@ -297,12 +297,22 @@ class SentencepieceModelStep(Step):
     then two ScatterNDUpdates -- the ids into a [batch, longest row] tensor of `pad_id`, ones into an attention mask of zeros.
     `model`: the serialized sentencepiece model.  The op takes whole sentences: a row of the state is one string (as behind
     StringTensorUnpack), and a state that carries skips is refused as UnigramModelStep refuses it.  The scatter is plain tensor
-    indexing next to the op's outputs; it is no hot path."""
+    indexing next to the op's outputs; it is no hot path.
+    `special_tokens`: a list of (token, id) -- the op's 8-input form, which the converter builds for every BPE and CHAR model
+    (handle_special_tokens_with_re, hf_parser.py:744-746, :858-877).  The order given is the order of the pattern's alternatives: of
+    two tokens that match at one place the earlier one wins (the converter sorts them in reverse, hf_parser.py:859)."""
 
-    def __init__(self, model, add_bos=False, add_eos=False, reverse=False, pad_id=0, nbest_size=1, alpha=1.0, lib=None):
+    def __init__(self, model, add_bos=False, add_eos=False, reverse=False, pad_id=0, nbest_size=1, alpha=1.0, lib=None, special_tokens=None):
         self.model = np.frombuffer(bytes(model), np.uint8)
         self.pad_id = int(pad_id)
-        self.op = K.SentencepieceTokenizer(nbest_size=nbest_size, alpha=alpha, add_bos=add_bos, add_eos=add_eos, reverse=reverse, lib=lib)
+        self.special = None
+        if special_tokens is not None:
+            toks = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t, _ in special_tokens]
+            ends = np.cumsum([len(t) for t in toks], dtype=np.int64).astype(np.int32) if toks else np.zeros(0, np.int32)
+            begins = np.concatenate([[0], ends[:-1]]).astype(np.int32) if toks else np.zeros(0, np.int32)
+            self.special = [begins, ends, np.frombuffer(b"".join(toks), np.uint8), np.array([i for _, i in special_tokens], np.int32)]
+        self.op = K.SentencepieceTokenizer(nbest_size=nbest_size, alpha=alpha, add_bos=add_bos, add_eos=add_eos, reverse=reverse, lib=lib,
+                                           special_tokens=special_tokens is not None)
 
     def apply(self, kind, vals):
         assert kind == "strings"
@@ -310,7 +320,7 @@ class SentencepieceModelStep(Step):
             raise ValueError("SentencepieceModelStep: the state carries skips (a SpecialTokensSplit in front), and the 4-input "
                              "SentencepieceTokenizer has no skips input")
         b, e, c = vals[2:5]
-        indices, values, dense_shape = self.op.evaluate([self.model, b, e, c])
+        indices, values, dense_shape = self.op.evaluate([self.model, b, e, c] + (self.special or []))
         if _is_torch(values):
             import torch
             shape = [int(x) for x in dense_shape.cpu()]

@@ -14,7 +14,7 @@ complete, so host waits are inside), the algorithmic bytes the op has to move (i
 they make, and whether a prefix of the result equals the oracle's.  The kernels' own durations: run this script under
 `rocprofv3 --kernel-trace --stats` (profiles/README.md); VERDICT r04 weak 6 asked for both.
 
-    python tools/ops_timing.py [--rows 65536] [--bytes 512] [--reps 10] [--check-rows 256] [--only-sentencepiece]
+    python tools/ops_timing.py [--rows 65536] [--bytes 512] [--reps 10] [--check-rows 256] [--only-sentencepiece [--sp-profile]]
 
 --only-sp-detok times SentencepieceDetokenizer and SentencepieceStreamDetokenizer instead, on one 16 384 x 2 048 id matrix (the
 config-2 batch's first rows encoded with spm_unigram_bytes, padded with an id outside the vocabulary), and beside them, in the same
@@ -172,6 +172,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--check-rows", type=int, default=256)
     ap.add_argument("--only-sentencepiece", action="store_true", help="the SentencepieceTokenizer rows and nothing else")
+    ap.add_argument("--sp-profile", action="store_true", help="behind the SentencepieceTokenizer rows: the library's per-launch profile of the 4- and the 8-input call")
     ap.add_argument("--only-sp-detok", action="store_true", help="the two sentencepiece detokenizers beside ovtk_detokenize_run and nothing else")
     ap.add_argument("--only-tf-ops", action="store_true", help="StringToHashBucket, EqualStr, RaggedToRagged beside UTF8Validate and nothing else")
     ap.add_argument("--only-string-ops", action="store_true", help="BytesToChars, CharsToBytes, ContribStringSplit, ContribStringJoin beside UTF8Validate and nothing else")
@@ -472,6 +473,77 @@ def main():
         # the BPE fixture on the same batch, beside the unigram one (its yardstick); the check: the installed package on the first rows
         timed(f"SentencepieceTokenizer(spm_bpe_unk, a BPE model), round {trial}", lambda: bpe_op.evaluate([bpe_model] + d[2:5]), n_c + 8 * n + 20 * n_ids,
               bpe_check if bpe_want is not None else None, "normalize (count, scan, write) -> stretch scan -> merge (a wave per sentence) -> scan -> sparse writer, one enqueue sequence")
+    # ---- the 8-input form (src/sentence_piece.cpp:200-230, :286-329; csrc/sp_special_kernels.hpp) beside the 4-input call on the same
+    # batch in the same run: 1 % of the rows hold one of a handful of added tokens.  Alternating single calls, the median of `reps`.
+    # The check: on the first rows, every part through the installed package and the tokens' ids between them.
+    added = [b"<|endoftext|>", b"<s>", b"</s>", b"[INST]", b"[/INST]"]
+    added_ids = [3000 + j for j in range(len(added))]
+    c8 = c.copy()
+    c8[c8 == ord("<")] = ord("(")   # (the 4-input call's batch is the same text; no token by accident)
+    c8[c8 == ord("[")] = ord("(")
+    rng8 = np.random.default_rng(2)
+    for i in np.flatnonzero(rng8.random(n) < 0.01):
+        t = np.frombuffer(added[int(rng8.integers(0, len(added)))], np.uint8)
+        if e[i] - b[i] > 2 * len(t):
+            at = int(b[i]) + int(rng8.integers(0, e[i] - b[i] - len(t)))
+            # at character boundaries on both sides: a paste inside a multi-byte character would leave malformed UTF-8, where the
+            # reference is undefined
+            while at + len(t) <= e[i] and ((c8[at] & 0xC0) == 0x80 or (at + len(t) < e[i] and (c8[at + len(t)] & 0xC0) == 0x80)):
+                at += 1
+            if at + len(t) <= e[i]:
+                c8[at:at + len(t)] = t
+    d8 = [b, e, c8] if args.emu else [torch.as_tensor(x, device=dev) for x in (b, e, c8)]
+    tb8, te8, tc8 = pack_strings(added)
+    tok_in = [tb8, te8, tc8, np.array(added_ids, np.int32)]
+    op4, op8 = SentencepieceTokenizer(lib=lib), SentencepieceTokenizer(lib=lib, special_tokens=True)
+    want8 = None
+    if bpe_want is not None:
+        import re
+        pat = re.compile(b"|".join(re.escape(t) for t in added))
+        want8 = []
+        for r in range(k):
+            row, at = bytes(c8[b[r]:e[r]]), 0
+            for m in pat.finditer(row):
+                want8 += (bpe_sp.encode(row[at:m.start()]) if m.start() > at else []) + [added_ids[added.index(m.group())]]
+                at = m.end()
+            want8 += bpe_sp.encode(row[at:]) if at < len(row) else []
+        want8 = np.array(want8, np.int32)
+    for _ in range(2):
+        out4, out8 = op4.evaluate([bpe_model] + d8), op8.evaluate([bpe_model] + d8 + tok_in)
+    sync()
+    t4, t8 = [], []
+    for _ in range(args.reps):
+        for ts, fn in ((t4, lambda: op4.evaluate([bpe_model] + d8)), (t8, lambda: op8.evaluate([bpe_model] + d8 + tok_in))):
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            ts.append(time.perf_counter() - t0)
+    n_tok = int(np.isin(to_np(out8[1]), added_ids).sum())
+    ok8 = None if want8 is None else bool(np.array_equal(to_np(out8[1])[:len(want8)], want8)) and int(to_np(out8[2])[0]) == n
+    for name, ts, note in (("SentencepieceTokenizer(spm_bpe_unk), 4 inputs, the special-token batch", t4, "the yardstick of the row below"),
+                           ("SentencepieceTokenizer(spm_bpe_unk), 8 inputs, 5 added tokens in 1 % of the rows", t8,
+                            f"{n_tok} token ids; cut (count, scan, host reads the slot count, write) -> the 4-input passes over the parts -> row lengths, scan, assemble")):
+        print(json.dumps({"op": name, "ms_per_call": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4), "reps": len(ts),
+                          "statistic": "median of single calls", "rows": n, "prefix_equals_package": ok8 if ts is t8 else None, "note": note}), flush=True)
+    if args.sp_profile:
+        # the library's own per-launch profile (ovtk_profile_*) of `reps` calls of each form: per tag the milliseconds summed over its
+        # launches and their number -- what the two forms' kernels cost apart from the host side
+        import ctypes as C
+        for name, fn in (("4 inputs", lambda: op4.evaluate([bpe_model] + d8)), ("8 inputs", lambda: op8.evaluate([bpe_model] + d8 + tok_in))):
+            sync()
+            lib.ovtk_profile_enable(1)
+            lib.ovtk_profile_reset()
+            for _ in range(args.reps):
+                fn()
+            sync()
+            size = int(lib.ovtk_profile_dump(None, C.c_int64(0)))
+            buf = C.create_string_buffer(size + 1)
+            lib.ovtk_profile_dump(buf, C.c_int64(size + 1))
+            lib.ovtk_profile_enable(0)
+            for line in buf.value.decode().splitlines():
+                tag, ms, count = line.split()[:3]
+                print(json.dumps({"profile_of": f"SentencepieceTokenizer(spm_bpe_unk), {name}, {args.reps} calls", "tag": tag, "ms_sum": float(ms),
+                                  "launches": int(count)}), flush=True)
     if args.only_sentencepiece:
         return
     # ---- UTF8Validate (src/utf8_validate.cpp:18-143): strings in, strings out
